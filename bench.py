@@ -9,8 +9,17 @@ before timing; a step is one ``plan.execute(executor, resume=True)`` of the
 mean's plan (every kernel and collective of the reduction), bracketed by
 barrier + synchronize.  value = input bytes of all ranks / time.
 
-``extra`` (same JSON line; each with its own ``roofline`` where one kernel
-dominates):
+A plain run (``--gpus N --steps K --warmup W``) does only that: set-up, W
+warm-up steps, K timed steps (``ms_per_step``), the result line.
+``--dump-outputs DIR`` also writes what the last timed step computed, the
+mean (720, 1440) f32 a caller of ``compute()`` receives, as
+``DIR/quad_means_mean.npy``; the inputs are seeded, so two builds can be
+compared output for output.  Everything below runs only with ``--full``: the
+headline's second, instrumented pass (per-launch times, ``roofline``), its
+value checks, the CPU baselines and the extras.
+
+``extra`` (``--full``; same JSON line; each with its own ``roofline`` where
+one kernel dominates):
 * ``rechunk`` -- configs[2]: 50000^2 f32 row chunks (1000, 50000) -> column
   chunks (50000, 1000), materialised, under the reference-shaped plan
   (``allowed_mem=2GB``: read -> intermediate -> write, 625 + 25 tasks,
@@ -33,7 +42,7 @@ holds 100 time chunks of u and v: one streaming launch + one RCCL reduce of
 the f64 totals, the count host-provided); the rechunk extras strong-scale (50000^2 total: pack -> one
 all_to_all over xGMI -> unpack; rechunk+mean reduces before the exchange).
 
-CPU baseline (rank 0, N=1 only): the oracle's restatement of the reference's
+CPU baseline (``--full``, rank 0, N=1 only): the oracle's restatement of the reference's
 executors (oracle/cubed_ref.py) on the SAME inputs copied back from HBM --
 sequential (PythonDagExecutor, runtime/executors/python.py:14-32) and
 threaded (AsyncPythonDagExecutor's ThreadPoolExecutor, min(32, ncpu + 4)
@@ -82,10 +91,15 @@ def parse(argv=None):
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--t-length", type=int, default=1000, help="time steps per GPU (quad-means)")
-    p.add_argument("--no-extra", action="store_true", help="headline only")
-    p.add_argument("--only", default="", help="comma list of extras to run (default: all)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-matmul", action="store_true", help="skip the matmul extras")
+    p.add_argument("--full", action="store_true",
+                   help="beyond the headline's timed steps: its per-launch pass, roofline and value checks, "
+                        "the CPU baselines and every extra workload (the options below select among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy")
+    p.add_argument("--no-extra", action="store_true", help="with --full: headline only")
+    p.add_argument("--only", default="", help="with --full: comma list of extras to run (default: all)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-matmul", action="store_true", help="with --full: skip the matmul extras")
     p.add_argument("--matmul-n", type=int, default=40000)
     p.add_argument("--backend", default="nccl",
                    help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse "
@@ -96,7 +110,10 @@ def parse(argv=None):
                    help="rechunk_mean_rehearsal: comma list of ranks to rehearse (default: all)")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                    help="per-launch HBM bytes from rocprofv3 PMC (see profiles/README.md)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.only and not args.full:
+        p.error("--only selects among the extras of a --full run")
+    return args
 
 
 # --------------------------------------------------------------------------- launch
@@ -206,18 +223,21 @@ def timed(fn, steps, world):
     return max_over_ranks((time.perf_counter() - t0) / steps, world)
 
 
-def timed_launches(ex, fn, steps, world):
+def timed_launches(ex, fn, steps, world, after_plain=None):
     """(seconds per call, {launch key: (count, mean ms)}).  Two passes of
     ``steps`` calls: the step time comes from the plain pass (what a user's
     compute runs: no instrumentation between the launches), the per-launch
     times from a second pass with the executor's HIP events around every
     launch (each event pair adds a few µs to the GPU timeline, which would
-    otherwise be charged to the step)."""
+    otherwise be charged to the step).  ``after_plain()`` runs between the
+    two passes (the outputs of the plain pass's last step are still there)."""
     from cubed_amd.runtime.executors.gpu import LaunchTimer
 
     global INSTR_DT, PLAIN_EVENT_MS
     dt = timed(fn, steps, world)
     PLAIN_EVENT_MS = EVENT_MS[0]
+    if after_plain is not None:
+        after_plain()
     host = list(HOST_US)
     ex.timing = LaunchTimer()
     INSTR_DT = timed(fn, steps, world)
@@ -565,9 +585,32 @@ def quad_means(args, rank, world, ex):
     step = step_fn(plan, ex, [m], (u, v))
     for _ in range(args.warmup):
         step()
-    dt, summ = timed_launches(ex, step, args.steps, world)
+
+    def dump():
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"quad_means_mean": full_host(m.zarray)}, rank)
+
+    if not args.full:
+        # the plain run: the timed steps and nothing after them
+        dt = timed(step, args.steps, world)
+        dump()
+        return dict(in_bytes=u.nbytes + v.nbytes, dt=dt, event_ms=EVENT_MS[0])
+    dt, summ = timed_launches(ex, step, args.steps, world, after_plain=dump)
     return dict(in_bytes=u.nbytes + v.nbytes, dt=dt, summ=summ, m=m, u=u, v=v, plain_event_ms=PLAIN_EVENT_MS,
                 symbols=launch_symbols(ex))
+
+
+def dump_outputs(path, arrays, rank):
+    """Write each of ``arrays`` (name -> host array, whole on every rank) as
+    ``path/<name>.npy`` from rank 0, float32 / float64 as computed."""
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def dominant(summ, kind):
@@ -1470,6 +1513,48 @@ def main(argv=None):
     dt = res["dt"]
     in_bytes = res["in_bytes"]
     value = in_bytes / dt / 1e9  # global input bytes: all ranks
+    line = {
+        "metric": "effective input GB/s (node) for fused elementwise+mean (quad-means)",
+        "value": round(value, 2),
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (on-GPU numpy-Philox U[0,1) inputs, bit-exact with cubed.random)",
+        "backend": args.backend if world > 1 else None,
+    }
+    if args.full:
+        full_line(args, rank, world, ex, res, line)
+    else:
+        line["config"] = headline_config(args, world)
+        line["gpu_ms_per_step"] = round(res["event_ms"], 4)
+        line["ranks"] = rank_info(args.backend)
+    rc = finish(line, CHECKS, rank, world)
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.destroy_process_group()
+    if rc:
+        sys.stderr.write(f"bench.py: value checks failed: {line['checks_failed']}\n")
+        sys.exit(rc)
+
+
+def headline_config(args, world):
+    return {"workload": "quad-means: mean(u*v, axis=0), u,v (1000,720,1440) f32 per GPU, "
+                        "chunks (10,720,1440), Spec(allowed_mem=2GB, reserved_mem=100MB)",
+            "t_length_per_gpu": args.t_length, "parallelism": f"block-cyclic dp{world}"}
+
+
+def full_line(args, rank, world, ex, res, line):
+    """--full: the headline's per-launch figures, roofline and value checks,
+    the CPU baseline and the extras, added to ``line``."""
+    dt = res["dt"]
+    in_bytes = res["in_bytes"]
     key, ms_instr = dominant(res["summ"], "FusedLaunch")
     kernels = [k for k in res["summ"] if k[2] not in ("_Alloc", "_Upload")]  # (host-only steps launch nothing)
     one_launch = kernels == [key] and res["summ"][key][0] == args.steps
@@ -1491,7 +1576,7 @@ def main(argv=None):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(res, ex)
         CHECKS.append(("quad-means", {"pass": cpu["gpu_matches_oracle_full_size"]}))
-    del res
+    res.clear()  # the caller's dict: drop the headline's arrays themselves
     free_gpu()
     wanted = [e for e in EXTRAS if not args.only or e in args.only.split(",")]
     if args.no_extra:
@@ -1532,26 +1617,11 @@ def main(argv=None):
             extra[name] = {"error": repr(e)}
             CHECKS.append((name, {"pass": False, "error": repr(e)}))
         free_gpu()
-    line = {
-        "metric": "effective input GB/s (node) for fused elementwise+mean (quad-means)",
-        "value": round(value, 2),
-        "unit": "GB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (on-GPU numpy-Philox U[0,1) inputs, bit-exact with cubed.random)",
-        "backend": args.backend if world > 1 else None,
-        "config": {"workload": "quad-means: mean(u*v, axis=0), u,v (1000,720,1440) f32 per GPU, "
-                               "chunks (10,720,1440), Spec(allowed_mem=2GB, reserved_mem=100MB)",
-                   "t_length_per_gpu": args.t_length, "parallelism": f"block-cyclic dp{world}",
-                   "extras_scaling": "strong: every extra keeps its total size as N grows (rechunk and "
-                                     "rechunk+mean 50000^2, config 1 20000^2, vorticity T=1000, matmul "
-                                     "40000^2); only the headline quad-means weak-scales"},
+    line.update({
+        "config": dict(headline_config(args, world),
+                       extras_scaling="strong: every extra keeps its total size as N grows (rechunk and "
+                                      "rechunk+mean 50000^2, config 1 20000^2, vorticity T=1000, matmul "
+                                      "40000^2); only the headline quad-means weak-scales"),
         "roofline": (roofline_hbm(algo, ms, "quad_means_fused", args,
                                   f"{key[0]}#{key[1]} ({key[2]}: {', '.join(symbols)}), "
                                   + (f"{ms:.4f} ms per launch from HIP events around the timed (plain) pass of "
@@ -1561,17 +1631,9 @@ def main(argv=None):
                      if world == 1 else roofline_step(algo, dt)),
         "extra": extra,
         "ranks": rank_info(args.backend),
-    }
+    })
     if cpu is not None:
         line["cpu_baseline"] = cpu
-    rc = finish(line, CHECKS, rank, world)
-    if world > 1:
-        import torch.distributed as dist
-
-        dist.destroy_process_group()
-    if rc:
-        sys.stderr.write(f"bench.py: value checks failed: {line['checks_failed']}\n")
-        sys.exit(rc)
 
 
 if __name__ == "__main__":

@@ -60,6 +60,28 @@ def test_single_gpu_runs_in_process(monkeypatch):
     bench.maybe_relaunch(args, ["--gpus", "1"])  # returns: runs here
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    args = bench.parse(["--full", "--only", "config1", "--dump-outputs", "d"])
+    assert args.full and args.only == "config1" and args.dump_outputs == "d"
+    with pytest.raises(SystemExit) as e:  # the extras exist only in a --full run
+        bench.parse(["--only", "config1"])
+    assert e.value.code == 2
+
+
+def test_dump_outputs_writes_rank_0_arrays_as_npy(tmp_path):
+    import numpy as np
+
+    a = np.arange(6, dtype=np.float32).reshape(2, 3)
+    bench.dump_outputs(str(tmp_path / "r1"), {"x": a}, rank=1)
+    assert not (tmp_path / "r1").exists()
+    bench.dump_outputs(str(tmp_path / "r0"), {"x": a, "n": np.arange(3)}, rank=0)
+    x, n = np.load(tmp_path / "r0" / "x.npy"), np.load(tmp_path / "r0" / "n.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, a)
+    assert n.dtype == np.float64 and np.array_equal(n, [0.0, 1.0, 2.0])
+
+
 def test_extras_selection():
     assert set(bench.EXTRAS) >= {"rechunk", "rechunk_mean", "config1", "vorticity", "matmul_f32",
                                  "matmul_bf16"}

@@ -9,7 +9,7 @@ set -o pipefail
 R="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd "$R" && mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline"
 cd /tmp
 timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof" -o run -- python3 "$R/bench.py" $ARGS > "$R/gpurun_out/prof.log" 2>&1 || { echo prof failed; tail -20 "$R/gpurun_out/prof.log"; exit 1; }
 echo prof-done
@@ -35,6 +35,7 @@ with open("gpurun_out/r06_kernel_sequence.txt", "w") as f:
 PY
 rm -rf gpurun_out/prof gpurun_out/pmc_fetch gpurun_out/pmc_write
 [ -n "$SKIP_BENCH" ] && { echo all-done; exit 0; }
-timeout -k 10 420 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { echo bench failed; tail -20 gpurun_out/bench.err; exit 1; }
-tail -c 300 gpurun_out/bench.json
+OUT="${OUT:-bench_out}" && mkdir -p "$OUT"
+timeout -k 10 420 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo bench failed; tail -20 "$OUT/bench.err"; exit 1; }
+tail -c 300 "$OUT/bench.json"
 echo all-done
