@@ -97,6 +97,14 @@ CUBED_DEV int64_t to_i64(V x) {
   else return f2i64((double)x);
 }
 
+// The bit pattern of a uint64 value: a float V holds the value itself (a
+// number in [0, 2^64)), an int64 V already holds the bits.
+template <typename V>
+CUBED_DEV int64_t to_u64bits(V x) {
+  if constexpr (is_same_v<V, int64_t>) return x;
+  else return ((double)x >= 9223372036854775808.0) ? (int64_t)(uint64_t)((double)x) : f2i64((double)x);
+}
+
 // Convert V to dtype dt and write it at p.
 template <typename V>
 CUBED_DEV void st1(char* p, int dt, V v) {
@@ -110,10 +118,7 @@ CUBED_DEV void st1(char* p, int dt, V v) {
     case CUBED_U16: *gstore_ptr<uint16_t>(p) = (uint16_t)to_i64(v); return;
     case CUBED_U32: *gstore_ptr<uint32_t>(p) = (uint32_t)to_i64(v); return;
     case CUBED_U64:
-      if constexpr (is_same_v<V, int64_t>) *gstore_ptr<uint64_t>(p) = (uint64_t)v;
-      else *gstore_ptr<uint64_t>(p) = ((double)v >= 9223372036854775808.0)
-                               ? (uint64_t)((double)v)
-                               : (uint64_t)to_i64(v);
+      *gstore_ptr<uint64_t>(p) = (uint64_t)to_u64bits(v);
       return;
     case CUBED_F32: *gstore_ptr<float>(p) = (float)v; return;
     case CUBED_F64: *gstore_ptr<double>(p) = (double)v; return;
@@ -271,6 +276,12 @@ CUBED_DEV int64_t imod(int64_t a, int64_t b) {
   int64_t r = a % b;
   if (r != 0 && ((r < 0) != (b < 0))) r += b;
   return r;
+}
+CUBED_DEV int64_t ufloordiv(int64_t a, int64_t b) {
+  return b == 0 ? (int64_t)0 : (int64_t)((uint64_t)a / (uint64_t)b);
+}
+CUBED_DEV int64_t umod(int64_t a, int64_t b) {
+  return b == 0 ? (int64_t)0 : (int64_t)((uint64_t)a % (uint64_t)b);
 }
 CUBED_DEV int64_t ipow(int64_t b, int64_t e) {
   if (e < 0) return 0;

@@ -48,7 +48,8 @@ CUBED_DEV void finish(const cubed_program_t& P, const cubed_task_t* T,
       if (f < P.nfields) {
         double X[VEC];
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) X[j] = P.field_acc[f] ? (double)acc[f][j].i : acc[f][j].f;
+        for (int j = 0; j < VEC; ++j) X[j] = P.field_acc[f] == 2 ? (double)(uint64_t)acc[f][j].i
+                                                        : P.field_acc[f] ? (double)acc[f][j].i : acc[f][j].f;
         put(er, f, X);
       }
     }

@@ -195,7 +195,8 @@ static int compile(JitKernel* k, const char* include_dirs) {
     return CUBED_E_JIT;
   }
   std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                                    "-DCUBED_JIT=1"};
+                                    // as the ahead-of-time build (Makefile): f32 / and sqrt round correctly
+                                    "-fhip-fp32-correctly-rounded-divide-sqrt", "-DCUBED_JIT=1"};
   std::string dirs = include_dirs ? include_dirs : "";
   size_t pos = 0;
   while (pos <= dirs.size()) {

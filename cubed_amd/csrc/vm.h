@@ -63,7 +63,9 @@ CUBED_DEV V cast_val(V x, int t, int s) {
       default: break;
     }
     // integer targets: float sources truncate toward zero, then wrap
-    int64_t i = dt_is_float(s) ? f2i64((double)x) : f2i64((double)x);
+    // (uint64: values in [2^63, 2^64) stay themselves, as in st1)
+    if (t == CUBED_U64 && (double)x >= 9223372036854775808.0) return (V)(uint64_t)((double)x);
+    int64_t i = f2i64((double)x);
     switch (t) {
       case CUBED_I8: return (V)(int8_t)i;
       case CUBED_I16: return (V)(int16_t)i;
@@ -159,6 +161,16 @@ CUBED_DEV void binary(int op, V (&X)[VEC], const V (&Y)[VEC]) {
       case CUBED_OP_BXOR: CUBED_EACH2(x ^ y); break;
       case CUBED_OP_SHL: CUBED_EACH2((y < 0 || y > 63) ? (int64_t)0 : (int64_t)((uint64_t)x << y)); break;
       case CUBED_OP_SHR: CUBED_EACH2((y < 0 || y > 63) ? (x < 0 ? (int64_t)-1 : (int64_t)0) : (x >> y)); break;
+      // uint64 operands: the registers hold their bit patterns
+      case CUBED_OP_UFLOORDIV: CUBED_EACH2(ufloordiv(x, y)); break;
+      case CUBED_OP_UMOD: CUBED_EACH2(umod(x, y)); break;
+      case CUBED_OP_UMAX: CUBED_EACH2((uint64_t)x > (uint64_t)y ? x : y); break;
+      case CUBED_OP_UMIN: CUBED_EACH2((uint64_t)x < (uint64_t)y ? x : y); break;
+      case CUBED_OP_ULT: CUBED_EACH2((int64_t)((uint64_t)x < (uint64_t)y)); break;
+      case CUBED_OP_ULE: CUBED_EACH2((int64_t)((uint64_t)x <= (uint64_t)y)); break;
+      case CUBED_OP_UGT: CUBED_EACH2((int64_t)((uint64_t)x > (uint64_t)y)); break;
+      case CUBED_OP_UGE: CUBED_EACH2((int64_t)((uint64_t)x >= (uint64_t)y)); break;
+      case CUBED_OP_USHR: CUBED_EACH2((uint64_t)y > 63 ? (int64_t)0 : (int64_t)((uint64_t)x >> y)); break;
       default: break;
     }
   } else {
@@ -191,6 +203,8 @@ CUBED_DEV void binary(int op, V (&X)[VEC], const V (&Y)[VEC]) {
       case CUBED_OP_COPYSIGN: CUBED_EACH2(copysign(x, y)); break;
       case CUBED_OP_LOGADDEXP: CUBED_EACH2(npy_logaddexp<V>(x, y)); break;
       case CUBED_OP_LOGADDEXP2: CUBED_EACH2(npy_logaddexp2<V>(x, y)); break;
+      // no shifts and no unsigned forms here: the host keeps them out of
+      // float-register programs (lowering.float_exact)
       default: break;
     }
   }
@@ -293,9 +307,14 @@ union Acc { double f; int64_t i; };
 CUBED_DEV Acc acc_init(int rop, int acc_i) {
   Acc a;
   switch (rop) {
-    case CUBED_R_MAX: if (acc_i) a.i = INT64_MIN; else a.f = -__builtin_inf(); break;
-    case CUBED_R_MIN: if (acc_i) a.i = INT64_MAX; else a.f = __builtin_inf(); break;
-    case CUBED_R_NANMAX: case CUBED_R_NANMIN: if (acc_i) a.i = (rop == CUBED_R_NANMAX ? INT64_MIN : INT64_MAX); else a.f = __builtin_nan(""); break;
+    // (acc_i == 2: the bits of a uint64, ordered as unsigned)
+    case CUBED_R_MAX: if (acc_i) a.i = acc_i == 2 ? (int64_t)0 : INT64_MIN; else a.f = -__builtin_inf(); break;
+    case CUBED_R_MIN: if (acc_i) a.i = acc_i == 2 ? (int64_t)-1 : INT64_MAX; else a.f = __builtin_inf(); break;
+    case CUBED_R_NANMAX: case CUBED_R_NANMIN:
+      if (acc_i == 2) a.i = (rop == CUBED_R_NANMAX ? (int64_t)0 : (int64_t)-1);
+      else if (acc_i) a.i = (rop == CUBED_R_NANMAX ? INT64_MIN : INT64_MAX);
+      else a.f = __builtin_nan("");
+      break;
     case CUBED_R_PROD: case CUBED_R_NANPROD: if (acc_i) a.i = 1; else a.f = 1.0; break;
     case CUBED_R_ALL: a.i = 1; break;
     case CUBED_R_SUM: case CUBED_R_NANSUM: if (acc_i) a.i = 0; else a.f = -0.0; break;
@@ -389,6 +408,16 @@ CUBED_DEV void pair_add(Acc& a0, Acc& a1, int rop, int acc_i, V v0, V v1) {
   pair_combine(a0, a1, b0, b1, rop, acc_i);
 }
 
+// max / min of two int64 accumulators (acc_i == 2: as uint64 bit patterns)
+CUBED_DEV int64_t imax_acc(int64_t a, int64_t b, int acc_i) {
+  return (acc_i == 2 ? (uint64_t)b > (uint64_t)a : b > a) ? b : a;
+}
+CUBED_DEV int64_t imin_acc(int64_t a, int64_t b, int acc_i) {
+  return (acc_i == 2 ? (uint64_t)b < (uint64_t)a : b < a) ? b : a;
+}
+template <typename V>
+CUBED_DEV int64_t acc_bits(V v, int acc_i) { return acc_i == 2 ? to_u64bits(v) : to_i64(v); }
+
 // fold one value into an accumulator
 template <typename V>
 CUBED_DEV void acc_add(Acc& a, int rop, int acc_i, V v) {
@@ -400,14 +429,14 @@ CUBED_DEV void acc_add(Acc& a, int rop, int acc_i, V v) {
     case CUBED_R_COUNT: a.i += 1; break;
     case CUBED_R_COUNT_NONNAN: a.i += (v == v) ? 1 : 0; break;
     case CUBED_R_MAX:
-      if (acc_i) { int64_t w = to_i64(v); a.i = w > a.i ? w : a.i; } else a.f = npy_max<double>(a.f, (double)v); break;
+      if (acc_i) a.i = imax_acc(a.i, acc_bits(v, acc_i), acc_i); else a.f = npy_max<double>(a.f, (double)v); break;
     case CUBED_R_MIN:
-      if (acc_i) { int64_t w = to_i64(v); a.i = w < a.i ? w : a.i; } else a.f = npy_min<double>(a.f, (double)v); break;
+      if (acc_i) a.i = imin_acc(a.i, acc_bits(v, acc_i), acc_i); else a.f = npy_min<double>(a.f, (double)v); break;
     case CUBED_R_NANMAX:
-      if (acc_i) { int64_t w = to_i64(v); a.i = w > a.i ? w : a.i; }
+      if (acc_i) a.i = imax_acc(a.i, acc_bits(v, acc_i), acc_i);
       else if (v == v) a.f = (a.f != a.f || (double)v > a.f) ? (double)v : a.f; break;
     case CUBED_R_NANMIN:
-      if (acc_i) { int64_t w = to_i64(v); a.i = w < a.i ? w : a.i; }
+      if (acc_i) a.i = imin_acc(a.i, acc_bits(v, acc_i), acc_i);
       else if (v == v) a.f = (a.f != a.f || (double)v < a.f) ? (double)v : a.f; break;
     case CUBED_R_PROD:
       if (acc_i) a.i = (int64_t)((uint64_t)a.i * (uint64_t)to_i64(v)); else a.f *= (double)v; break;
@@ -426,13 +455,13 @@ CUBED_DEV Acc acc_combine(Acc a, Acc b, int rop, int acc_i) {
     case CUBED_R_SUM: case CUBED_R_NANSUM:
       if (acc_i) r.i = (int64_t)((uint64_t)a.i + (uint64_t)b.i); else r.f = a.f + b.f; break;
     case CUBED_R_COUNT: case CUBED_R_COUNT_NONNAN: r.i = a.i + b.i; break;
-    case CUBED_R_MAX: if (acc_i) r.i = a.i > b.i ? a.i : b.i; else r.f = npy_max<double>(a.f, b.f); break;
-    case CUBED_R_MIN: if (acc_i) r.i = a.i < b.i ? a.i : b.i; else r.f = npy_min<double>(a.f, b.f); break;
+    case CUBED_R_MAX: if (acc_i) r.i = imax_acc(a.i, b.i, acc_i); else r.f = npy_max<double>(a.f, b.f); break;
+    case CUBED_R_MIN: if (acc_i) r.i = imin_acc(a.i, b.i, acc_i); else r.f = npy_min<double>(a.f, b.f); break;
     case CUBED_R_NANMAX:
-      if (acc_i) r.i = a.i > b.i ? a.i : b.i;
+      if (acc_i) r.i = imax_acc(a.i, b.i, acc_i);
       else r.f = (a.f != a.f) ? b.f : ((b.f != b.f) ? a.f : (a.f > b.f ? a.f : b.f)); break;
     case CUBED_R_NANMIN:
-      if (acc_i) r.i = a.i < b.i ? a.i : b.i;
+      if (acc_i) r.i = imin_acc(a.i, b.i, acc_i);
       else r.f = (a.f != a.f) ? b.f : ((b.f != b.f) ? a.f : (a.f < b.f ? a.f : b.f)); break;
     case CUBED_R_PROD: case CUBED_R_NANPROD:
       if (acc_i) r.i = (int64_t)((uint64_t)a.i * (uint64_t)b.i); else r.f = a.f * b.f; break;

@@ -448,13 +448,23 @@ class Codegen:
             return self._finish(e, r, rounded=True)
         if isinstance(e, ir.Unary):
             r = self.owned(*self.gen(e.x))
+            if self.vtype == V_I64 and np.dtype(e.x.dtype) == np.uint64 and e.op in ("abs", "sign"):
+                # the register holds uint64 bits: |x| = x, sign(x) = (x != 0)
+                if e.op == "sign":
+                    self.code.append((ir_op("CAST"), r, 0, 0, ir.dtype_code(np.bool_), ir.dtype_code(e.x.dtype)))
+                return self._finish(e, r)
             self.code.append((ir.UNARY_OPS[e.op], r, 0, 0, 0, 0))
             return self._finish(e, r)
         if isinstance(e, ir.Binary):
             ra, oa = self.gen(e.a)
             ra = self.owned(ra, oa)
             rb, ob = self.gen(e.b)
-            self.code.append((ir.BINARY_OPS[e.op], ra, rb, 0, 0, 0))
+            op = ir.BINARY_OPS[e.op]
+            if self.vtype == V_I64 and np.dtype(e.a.dtype) == np.uint64:
+                # the registers hold uint64 bit patterns: order, divide and
+                # shift them as unsigned
+                op = _UNSIGNED_OPS.get(e.op, op)
+            self.code.append((op, ra, rb, 0, 0, 0))
             if ob:
                 self.release(rb)
             return self._finish(e, ra)
@@ -503,6 +513,10 @@ class Codegen:
 
 
 _OPCODES = {"NOP": 0, "CONST": 1, "MOV": 2, "CAST": 3, "WHERE": 4}
+# uint64 operands in int64 registers (include/cubed_amd.h CUBED_OP_UFLOORDIV..)
+_UNSIGNED_OPS = {"floor_divide": 94, "remainder": 95, "maximum": 96, "minimum": 97, "fmax": 96, "fmin": 97,
+                 "less": 98, "less_equal": 99, "greater": 100, "greater_equal": 101,
+                 "bitwise_right_shift": 102}
 
 
 def ir_op(name):
@@ -511,7 +525,7 @@ def ir_op(name):
 
 def choose_vtype(exprs, leaves) -> int:
     """Register value type: I64 for all-integer programs, F32 when every
-    computed node is f32-or-narrower (f64 leaves only feed casts to f32), else
+    computed node is f32-or-narrower (f64 leaves only feed casts to f32 / bf16), else
     F64 (f32 nodes are then re-rounded by CAST, exact for + - * / sqrt)."""
     nodes = []
     seen = set()
@@ -541,6 +555,12 @@ def choose_vtype(exprs, leaves) -> int:
             if d not in small and not all(isinstance(p, ir.Cast) and np.dtype(p.dtype) in small
                                           for p in parents.get(id(n), [None])):
                 ok = False
+            if d == np.float64 and any(np.dtype(p.dtype) not in (np.dtype(np.float32), ir.bfloat16)
+                                       for p in parents.get(id(n), [])):
+                # the f32 load of an f64 leaf is its cast to f32; a cast to
+                # f16, an integer or bool rounds (truncates, tests) the f64
+                # value itself
+                ok = False
         elif isinstance(n, (ir.BlockOffset, ir.Iota)):
             ok = False
         elif isinstance(n, ir.Const):
@@ -548,6 +568,95 @@ def choose_vtype(exprs, leaves) -> int:
         elif d not in small:
             ok = False
     return V_F32 if ok else V_F64
+
+
+# ---- integer nodes in float registers
+# A program with a float leaf or node runs in float registers, its integer
+# nodes too.  That is only right where the float op on the integers' values is
+# exact: the values must fit the mantissa (24 / 53 bits), the op's full result
+# too (the CAST after it wraps it as the integer op would), and the op must
+# have a float form that means the same.  Everything else is kept out of
+# float-register programs: the producer fusion refuses it (program_fits) and a
+# single program is split so the integer part runs in int64 registers
+# (cubed_amd/split.py).
+_MANTISSA = {V_F32: 24, V_F64: 53}
+_INT_SAME_WIDTH = {"negative", "abs", "positive", "sign", "floor", "ceil", "trunc", "round", "isnan", "isinf",
+                   "isfinite", "signbit", "logical_not", "bitwise_invert", "maximum", "minimum", "fmax", "fmin",
+                   "equal", "not_equal", "less", "less_equal", "greater", "greater_equal", "logical_and",
+                   "logical_or", "logical_xor", "bitwise_and", "bitwise_or", "bitwise_xor"}
+_INT_ONE_MORE_BIT = {"add", "subtract"}
+_INT_DOUBLE_WIDTH = {"multiply", "square"}
+
+
+def _int_bits(dt) -> int:
+    dt = np.dtype(dt)
+    return dt.itemsize * 8 if dt.kind in "iu" else (1 if dt.kind == "b" else 0)
+
+
+def float_exact(exprs, vtype) -> bool:
+    """Whether every integer-typed node of ``exprs`` computes in the float
+    registers of ``vtype`` what it would in integer arithmetic.  Each integer
+    value gets a bound on its magnitude in bits (its dtype's width; index
+    leaves and constants: their own); an op is exact when its operands and its
+    unwrapped result stay within the mantissa."""
+    if vtype == V_I64:
+        return True
+    m = _MANTISSA[vtype]
+    memo: Dict[int, Optional[int]] = {}
+
+    class Inexact(Exception):
+        pass
+
+    def bits(e) -> int:
+        """Bound on |value| in bits of an integer / bool node (0: a float)."""
+        if id(e) not in memo:
+            memo[id(e)] = node_bits(e)
+        return memo[id(e)]
+
+    def node_bits(e) -> int:
+        w = _int_bits(e.dtype)
+        if isinstance(e, ir.Const):
+            return min(w, max(abs(int(e.value)).bit_length(), 1)) if w else 0
+        if isinstance(e, ir.Iota):
+            return int(sum(e.chunks[e.dim])).bit_length()
+        if isinstance(e, ir.BlockOffset):
+            return max(int(np.prod(e.numblocks, dtype=np.int64)).bit_length(), 1)
+        if isinstance(e, ir.LEAF_TYPES):
+            return w
+        ch = [bits(c) for c in e.children()]
+        if isinstance(e, ir.Cast):
+            c, t = e.x, np.dtype(e.dtype)
+            if ch[0] > m and t.kind != "b":
+                # a wide integer leaf is rounded once by its load; the CAST
+                # after it must not round again (or wrap what was rounded)
+                if not (isinstance(c, (ir.Arg, ir.Region)) and ir.is_float(t) and
+                        (t == np.float64 or t == np.float16 or vtype == V_F32)):
+                    raise Inexact
+            return min(ch[0], w) if ch[0] else w
+        if isinstance(e, ir.Where):
+            if max(ch[1:]) > m:
+                raise Inexact
+            return max(ch[1:])
+        ops = [_int_bits(c.dtype) for c in e.children()]
+        if not any(o > 1 for o in ops):
+            return w  # bool and float operands
+        b = max(ch)
+        if e.op in _INT_ONE_MORE_BIT:
+            b += 1
+        elif e.op in _INT_DOUBLE_WIDTH:
+            b = sum(ch) if len(ch) == 2 else 2 * b
+        elif e.op not in _INT_SAME_WIDTH:
+            raise Inexact  # floor_divide, remainder, pow, shifts: integer registers only
+        if b > m:
+            raise Inexact
+        return min(b, w) if w else 0
+
+    try:
+        for e in exprs:
+            bits(e)
+    except Inexact:
+        return False
+    return True
 
 
 def collect_leaves(exprs) -> List[Any]:
@@ -622,7 +731,10 @@ def program_fits(p: ir.ExprProgram) -> bool:
             for lf in ir.leaves(e):
                 if not isinstance(lf, (ir.Const, ir.Field)):
                     leaf_regs[id(lf)] = by_key[_leaf_key(lf)]
-        cg = Codegen(choose_vtype(pre, leaves), leaf_regs)
+        vtype = choose_vtype(pre, leaves)
+        if not float_exact(pre, vtype):
+            return False
+        cg = Codegen(vtype, leaf_regs)
         cg.count_uses(pre)
         for e in pre:
             cg.pin(cg.gen(e)[0])  # as the lowering does: outputs stay live
@@ -918,6 +1030,8 @@ class Lowerer:
             # cubed_task_t carries one Philox key per task
             raise LoweringError("fused program draws from more than one random stream")
         vtype = choose_vtype(pre_exprs, leaves)
+        if not float_exact(pre_exprs, vtype):
+            raise LoweringError(f"{program.name}: integer arithmetic that float registers would not keep exact")
         leaf_regs = {}
         by_key = {_leaf_key(l): i for i, l in enumerate(leaves)}
 
@@ -955,6 +1069,8 @@ class Lowerer:
                 P.field_src[i] = r
                 P.field_rop[i] = ir.ROPS[f.rop]
                 P.field_acc[i] = 1 if ir.acc_is_int(f.rop, f.dtype) else 0
+                if np.dtype(f.dtype) == np.uint64 and f.rop in ("max", "min", "nanmax", "nanmin"):
+                    P.field_acc[i] = 2  # the accumulator is ordered as unsigned
             # epilogue over fields (double registers 0..nf-1)
             fidx = {f.name: i for i, f in enumerate(rfields)}
             direct = all(isinstance(e, ir.Field) for _, e in out_items)

@@ -32,8 +32,10 @@ import itertools
 from types import SimpleNamespace
 from typing import Dict, List, Optional
 
+import numpy as np
+
 from . import ir
-from .lowering import LoweringError, collect_leaves, program_fits
+from .lowering import LoweringError, choose_vtype, collect_leaves, float_exact, program_fits
 from .primitive.types import CubedArrayProxy
 from .storage import DeviceArray
 
@@ -76,11 +78,29 @@ def pick_subexpr(p: ir.ExprProgram) -> Optional[ir.Expr]:
     for e in pre:
         _nodes(e, nodes, seen)
     best, best_key = None, None
+    # integer arithmetic that the program's float registers would not keep
+    # exact (lowering.float_exact): the largest part that is exact by itself
+    # goes first, all-integer parts (int64 registers) before any other, until
+    # what is left is exact too
+    inexact = not float_exact(pre, choose_vtype(pre, collect_leaves(pre)))
     for e in nodes:
         if isinstance(e, ir.LEAF_TYPES):
             continue
         lv = collect_leaves([e])
-        if len(lv) < 2 or any(not type(l) is ir.Arg for l in lv):
+        if (len(lv) < 2 and not inexact) or any(not type(l) is ir.Arg for l in lv):
+            continue
+        if inexact:
+            if any(e is x for x in pre):
+                continue
+            sub = ir.ExprProgram(ndim=p.ndim, nargs=p.nargs, outputs=e, out_axes=tuple(range(p.ndim)),
+                                 name=f"{p.name}/part")
+            if not program_fits(sub):
+                continue
+            sub_nodes = collect_leaves_nodes(e)
+            all_int = all(np.dtype(n.dtype).kind in "biu" for n in sub_nodes)
+            k = (all_int, len(sub_nodes))
+            if best_key is None or k > best_key:
+                best, best_key = e, k
             continue
         sub = ir.ExprProgram(ndim=p.ndim, nargs=p.nargs, outputs=e, out_axes=tuple(range(p.ndim)),
                              name=f"{p.name}/part")

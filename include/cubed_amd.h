@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define CUBED_ABI_VERSION 16
+#define CUBED_ABI_VERSION 17
 
 #define CUBED_MAX_DIMS 6   /* iteration dims of one task after coalescing   */
 #define CUBED_MAX_LEAVES 4 /* array/philox/const-array inputs of a program  */
@@ -143,7 +143,11 @@ enum cubed_op {
   CUBED_OP_GE, CUBED_OP_LAND, CUBED_OP_LOR, CUBED_OP_LXOR, CUBED_OP_BAND,
   CUBED_OP_BOR, CUBED_OP_BXOR, CUBED_OP_SHL, CUBED_OP_SHR, CUBED_OP_ATAN2,
   CUBED_OP_HYPOT, CUBED_OP_LOGADDEXP, CUBED_OP_COPYSIGN, CUBED_OP_FMAX,
-  CUBED_OP_FMIN, CUBED_OP_LOGADDEXP2
+  CUBED_OP_FMIN, CUBED_OP_LOGADDEXP2,
+  /* uint64 operands in int64 registers (ABI 17): the register holds the bit
+   * pattern, these read it as unsigned */
+  CUBED_OP_UFLOORDIV, CUBED_OP_UMOD, CUBED_OP_UMAX, CUBED_OP_UMIN, CUBED_OP_ULT,
+  CUBED_OP_ULE, CUBED_OP_UGT, CUBED_OP_UGE, CUBED_OP_USHR
 };
 
 typedef struct {
@@ -190,7 +194,9 @@ typedef struct {
   uint8_t leaf_dtype[CUBED_MAX_LEAVES];
   int32_t nfields;               /* 0 = map (no reduction)                  */
   uint8_t field_rop[CUBED_MAX_FIELDS];
-  uint8_t field_acc[CUBED_MAX_FIELDS]; /* 0 = f64 accumulator, 1 = i64     */
+  uint8_t field_acc[CUBED_MAX_FIELDS]; /* 0 = f64 accumulator, 1 = i64,     */
+                                       /* 2 = i64 bits of a uint64 (ABI 17: */
+                                       /* max / min order it as unsigned)   */
   uint8_t field_src[CUBED_MAX_FIELDS]; /* register holding the field value  */
   uint8_t pad0[3];
   int32_t nouts;

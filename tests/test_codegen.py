@@ -111,3 +111,194 @@ def test_common_subexpression_handed_over_at_last_use():
         regs[i] = np.full(8, np.nan)
     run(cg.code, regs)
     assert np.array_equal(regs[r], np.exp(vals[0]) * vals[1] + (np.exp(vals[0]) - vals[2]))
+
+
+# --------------------------------------------------------------------------
+# Elementwise conformance on the host: every op x dtype x fused form is
+# lowered as the executor lowers it, run on the model of the VM (vm_model.py)
+# and compared with numpy evaluating the same expression tree.
+import pytest
+
+import vm_model as M
+from cubed_amd import lowering as L
+
+N = 800  # elements per case: the edge product (at most 24 x 24) + random fill
+FORMS = ["alone", "astype_f32", "astype_f64", "where"]
+
+
+def op_program(op, dtype):
+    dt = np.dtype(dtype)
+    nargs = 1 if op in ir.UNARY_OPS else 2
+    return ir.elementwise_program(op, [dt] * nargs, [1] * nargs, M.result_dtype(op, dt)), nargs
+
+
+def form_program(op, dtype, form):
+    """(program, number of array args) of ``op`` alone / followed by astype /
+    feeding where(signbit(f32), op(..), y)."""
+    p, nargs = op_program(op, dtype)
+    rdt = M.result_dtype(op, dtype)
+    if form == "alone":
+        return p, nargs, 0
+    if form.startswith("astype"):
+        to = np.dtype("f4") if form.endswith("f32") else np.dtype("f8")
+        c = ir.elementwise_program("astype", [rdt], [1], to)
+        return ir.fuse_programs(c, [p], [nargs]), nargs, 0
+    cond = ir.elementwise_program("signbit", [np.dtype("f4")], [1], np.bool_)
+    w = ir.elementwise_program("where", [np.dtype(bool), rdt, rdt], [1, 1, 1], rdt)
+    # args: cond's f32, the op's, then y (4 leaves at most: one fused program)
+    return ir.fuse_programs(w, [cond, p, None], [1, nargs, 1]), nargs, 1
+
+
+def form_arrays(op, dtype, form, nargs, n=N):
+    xs = list(M.binary_inputs(op, dtype, n)) if nargs == 2 else [M.unary_inputs(op, dtype, n)]
+    if form != "where":
+        return xs
+    rng = np.random.default_rng(3)
+    c0 = rng.standard_normal(n).astype("f4")
+    rdt = M.result_dtype(op, dtype)
+    y = M.random_fill(rdt, n, 9)
+    return [c0] + xs + [y]
+
+
+def check(op, dtype, got, exp, what):
+    if M.is_ulp(op, dtype):
+        # the model runs numpy's routine in the register type: equal up to
+        # the routine's own rounding (the GPU tests bound the device's error)
+        ok = np.isfinite(exp)
+        assert np.array_equal(np.isnan(got), np.isnan(exp)), what
+        assert np.array_equal(got[~ok], exp[~ok], equal_nan=True), what
+        g, e = got[ok].astype("f8"), exp[ok].astype("f8")
+        fi = np.finfo(dtype)  # 2 ulps of the op's own dtype
+        # (logaddexp = max + log1p(..) in [max, max + 0.7]: a result near 0
+        # still carries the rounding of a sum of operands of size <= 0.7)
+        floor = 1.0 if op.startswith("logaddexp") else fi.tiny
+        tol = 2 * np.spacing(np.maximum(np.abs(exp[ok]), floor).astype(fi.dtype)).astype("f8")
+        assert np.all(np.abs(g - e) <= tol), (what, np.abs(g - e).max())
+    elif op in M.ZERO_SIGN_FREE:
+        M.assert_value_equal(got, exp, what)
+    else:
+        M.assert_bit_equal(got, exp, what)
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("dtype", [d.name for d in M.REAL_DTYPES])
+def test_model_matches_numpy(dtype, form):
+    """Every op valid at ``dtype``, in one fused form.  Pins the host half of
+    the lowering: the register type, the CAST placement, the uint64 opcodes,
+    and which integer nodes may run in float registers."""
+    un, bi = M.ops_for(dtype)
+    failures = []
+    for op in un + bi:
+        p, nargs, off = form_program(op, dtype, form)
+        arrays = form_arrays(op, dtype, form, nargs)
+        exp = M.np_eval(p.outputs, arrays)
+        try:
+            got, vtypes = M.model_eval(p, arrays)
+            check(op, dtype, got, exp, (op, dtype, form, vtypes))
+        except (AssertionError, M.UnknownOpcode) as e:
+            failures.append(f"{op}: {type(e).__name__} {str(e)[:200]}")
+    assert not failures, "\n".join(failures)
+
+
+def test_model_refuses_unknown_opcodes():
+    with pytest.raises(M.UnknownOpcode):
+        M.run_code([(15, 0, 0, 0, 0, 0)], [], L.V_F64, {0: np.zeros(2)})
+    with pytest.raises(M.UnknownOpcode):  # vm.h has no float case for shifts
+        M.run_code([(ir.BINARY_OPS["bitwise_left_shift"], 0, 1, 0, 0, 0)], [], L.V_F64,
+                   {0: np.ones(2), 1: np.ones(2)})
+
+
+def test_model_covers_every_opcode():
+    """Each name of ir.UNARY_OPS / ir.BINARY_OPS is run by the matrix above
+    at some dtype, and the model has it in both register kinds it can reach."""
+    un, bi = set(), set()
+    for d in M.REAL_DTYPES:
+        u, b = M.ops_for(d)
+        un |= set(u)
+        bi |= set(b)
+    assert un == set(ir.UNARY_OPS) and bi == set(ir.BINARY_OPS)
+    assert set(M.FLOAT_UNARY) == set(ir.UNARY_OPS) - {"positive"}
+    assert set(M.FLOAT_BINARY) == set(ir.BINARY_OPS) - {"bitwise_left_shift", "bitwise_right_shift"}
+
+
+def test_integer_shift_never_runs_in_float_registers():
+    """astype(i32 << i32, f64): the shift is its own int64 program."""
+    p, nargs, _ = form_program("bitwise_left_shift", "i4", "astype_f64")
+    assert not L.program_fits(p)
+    from cubed_amd.split import split_program
+
+    parts, rest = split_program(p)
+    assert [M.lower(s)[0] for s, _ in parts] == [L.V_I64] and parts[0][1] == np.dtype("i4")
+    assert M.lower(rest)[0] == L.V_F64
+
+
+def test_exact_integer_fusions_stay_fused():
+    """int8 / int16 add in f32 registers and where() between int32 leaves in
+    f64 registers are exact there: one program, as before."""
+    for op, dt, form in [("add", "i1", "astype_f32"), ("subtract", "i2", "astype_f32"),
+                         ("add", "u1", "where"), ("maximum", "i4", "astype_f64"), ("less", "i4", "where")]:
+        p, _, _ = form_program(op, dt, form)
+        assert L.program_fits(p), (op, dt, form)
+
+
+def test_uint64_uses_unsigned_opcodes():
+    for op, code in L._UNSIGNED_OPS.items():
+        p, _ = op_program(op, "u8")
+        vtype, cg, _, _, _ = M.lower(p)
+        assert vtype == L.V_I64 and code in [c[0] for c in cg.code], op
+        p, _ = op_program(op, "i8")
+        assert code not in [c[0] for c in M.lower(p)[1].code], op
+
+
+@pytest.mark.parametrize("src", [d.name for d in M.REAL_DTYPES])
+def test_model_cast_matrix(src):
+    """astype from ``src`` to each real dtype on the model, against numpy's
+    astype: the register type must keep the source's value (an f64 leaf cast
+    to bool or an integer does not go through an f32 register)."""
+    for dst in M.REAL_DTYPES:
+        x = M.cast_source(src, dst, 400)
+        p = ir.elementwise_program("astype", [np.dtype(src)], [1], dst)
+        with np.errstate(all="ignore"):
+            exp = x.astype(dst)
+        got, _ = M.model_eval(p, [x]) if np.dtype(src) != dst else (x, None)
+        M.assert_bit_equal(got, exp, (src, dst.name))
+
+
+def test_f64_to_f16_rounds_once():
+    """astype(f64, f16) must not round through an f32 register: 1 + 2^-11 +
+    2^-30 rounds up to 1 + 2^-10, through f32 it would tie down to 1."""
+    p = ir.elementwise_program("astype", [np.dtype("f8")], [1], np.dtype("f2"))
+    x = np.array([1 + 2.0 ** -11 + 2.0 ** -30, -(1 + 2.0 ** -11 + 2.0 ** -30), 0.1])
+    got, vtypes = M.model_eval(p, [x])
+    assert vtypes == [L.V_F64]
+    M.assert_bit_equal(got, x.astype("f2"))
+
+
+def test_headline_programs_lower_as_before():
+    """mean((x + 1) * 2) in f32, mean(u * v) in f64 and the vorticity chain
+    a * x + b * y keep their register type and instruction list."""
+    f4, f8 = np.dtype("f4"), np.dtype("f8")
+    x = ir.Arg(0, f4, (0, 1))
+    e1 = ir.Binary("multiply", ir.Binary("add", x, ir.Const(1.0, f4), f4), ir.Const(2.0, f4), f4)
+    u, v = ir.Arg(0, f8, (0, 1)), ir.Arg(1, f8, (0, 1))
+    e2 = ir.Binary("multiply", u, v, f8)
+    a, xx, b, y = (ir.Arg(i, f8, (0, 1)) for i in range(4))
+    e3 = ir.Binary("add", ir.Binary("multiply", a, xx, f8), ir.Binary("multiply", b, y, f8), f8)
+    ADD, MUL, CONST = ir.BINARY_OPS["add"], ir.BINARY_OPS["multiply"], L._OPCODES["CONST"]
+    expect = [
+        (e1, 1, L.V_F32, [(CONST, 1, 0, 0, 0, 0), (ADD, 0, 1, 0, 0, 0), (CONST, 1, 0, 0, 0, 1), (MUL, 0, 1, 0, 0, 0)]),
+        (e2, 2, L.V_F64, [(MUL, 0, 1, 0, 0, 0)]),
+        (e3, 4, L.V_F64, [(MUL, 0, 1, 0, 0, 0), (MUL, 2, 3, 0, 0, 0), (ADD, 0, 2, 0, 0, 0)]),
+    ]
+    for e, nargs, vt, code in expect:
+        p = ir.reduce_program(2, e.dtype, (0,), [("n", "count", np.int64), ("total", "sum", np.float64)],
+                              structured=True, value=e)
+        assert L.program_fits(p)
+        pre = L.dedupe_leaves([f.expr for f in p.reduce.fields])
+        leaves = L.collect_leaves(pre)
+        assert L.choose_vtype(pre, leaves) == vt
+        assert L.float_exact(pre, vt)
+        cg = L.Codegen(vt, {id(lf): i for i, lf in enumerate(leaves)})
+        cg.count_uses(pre[:1])
+        cg.gen(pre[0])
+        assert cg.code == code, cg.code
