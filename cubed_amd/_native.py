@@ -37,7 +37,7 @@ MAX_EPI = 16
 MAX_CONSTS = 16
 NREGS = 6
 
-ABI_VERSION = 17  # include/cubed_amd.h CUBED_ABI_VERSION
+ABI_VERSION = 18  # include/cubed_amd.h CUBED_ABI_VERSION
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcubed_amd.so")
 
 
@@ -97,6 +97,16 @@ GEMM_AUTO, GEMM_ANY, GEMM_MFMA = -1, 0, 1
 
 COPY_ROWS, COPY_ELEMS, COPY_TILE, COPY_FLAT = 0, 1, 2, 3
 
+# cubed_scan_task_t (one chunk of a prefix sum, seen as (outer, n, inner))
+SCAN_TASK_DTYPE = np.dtype([
+    ("src_base", np.int64), ("dst_base", np.int64), ("carry_base", np.int64),
+    ("outer", np.int64), ("n", np.int64), ("inner", np.int64),
+    ("src_outer_stride", np.int64), ("src_n_stride", np.int64),
+    ("dst_outer_stride", np.int64), ("dst_n_stride", np.int64),
+    ("carry_outer_stride", np.int64),
+])
+SCAN_ROWS, SCAN_COLS, SCAN_COLS_V4 = 0, 1, 2
+
 
 class NativeError(RuntimeError):
     pass
@@ -129,6 +139,10 @@ def lib():
     L.cubed_copy_boxes.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
                                    c_int64, c_int64, c_void_p]
     L.cubed_copy_boxes.restype = c_int
+    L.cubed_scan_path.argtypes = [c_void_p, c_int64, c_int32]
+    L.cubed_scan_path.restype = c_int
+    L.cubed_scan_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_scan_chunks.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -229,8 +243,17 @@ EXPORTED_SYMBOLS = (
     "cubed_blosc_compress", "cubed_zstd_decompress", "cubed_lz4_chunk_decompress", "cubed_gemm_chain", "cubed_gemm_chain_path",
     "cubed_gemm_grid_check", "cubed_gemm_chain_grid", "cubed_gemm_pack_bytes", "cubed_gemm_chain_packed",
     "cubed_gemm_dist_image_bytes", "cubed_gemm_dist_pack_a", "cubed_gemm_dist_b_bytes", "cubed_gemm_dist_pack_b",
-    "cubed_gemm_dist_gemm",
+    "cubed_gemm_dist_gemm", "cubed_scan_path", "cubed_scan_chunks",
 )
+
+
+def scan_path(rows: np.ndarray, vtype: int) -> int:
+    """The kernel a host table of SCAN_TASK_DTYPE rows takes (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=SCAN_TASK_DTYPE)
+    path = lib().cubed_scan_path(rows.ctypes.data, len(rows), vtype)
+    if path < 0:
+        check(path, "cubed_scan_path")
+    return path
 
 
 INCLUDE_DIRS = ";".join([os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"),

@@ -8,13 +8,15 @@ import numpy as np
 
 from ..chunkfuncs import (NumpyReduction, _mean_aggregate, _mean_combine, _mean_func, _var_combine,
                           _var_func, _VarAggregate)
-from ..core import reduction
+from ..core import reduction, scan
+from ..core.ops import validate_axis
 from .dtypes import (
     _numeric_dtypes,
     _real_floating_dtypes,
     _real_numeric_dtypes,
     _signed_integer_dtypes,
     _unsigned_integer_dtypes,
+    bfloat16,
     complex64,
     complex128,
     float32,
@@ -81,6 +83,48 @@ def sum(x, /, *, axis=None, dtype=None, keepdims=False):
         dtype = _default_sum_dtype(x.dtype)
     return reduction(x, _np_sum, axis=axis, dtype=dtype, keepdims=keepdims,
                      extra_func_kwargs=dict(dtype=dtype))
+
+
+def cumulative_sum(x, /, *, axis=None, dtype=None, include_initial=False):
+    """Array API ``cumulative_sum`` (2023.12; not in the reference v0.12.0):
+    numpy's ``cumsum`` along one axis, same shape and chunks as ``x``.
+
+    Unlike ``sum``, float32 stays float32 (the result is full-size); signed
+    integers give int64, unsigned ones uint64.  The scan itself runs on
+    float32, float64 or 64-bit integer values -- floats always accumulate in
+    float64 -- so any other input or requested dtype is converted by an
+    ``astype`` before or after it (a wrapped 64-bit sum truncated to a narrow
+    integer is the wrapped narrow sum)."""
+    from .data_type_functions import astype
+
+    if x.dtype not in _real_numeric_dtypes or x.dtype == bfloat16:
+        raise TypeError("Only real numeric dtypes (other than bfloat16) are allowed in cumulative_sum")
+    if dtype is None:
+        dtype = x.dtype if x.dtype in (float32, float64) else _default_sum_dtype(x.dtype)
+    elif np.dtype(dtype) not in _real_numeric_dtypes or np.dtype(dtype) == bfloat16:
+        raise TypeError("Only real numeric dtypes (other than bfloat16) are allowed as the dtype "
+                        "of cumulative_sum")
+    dtype = np.dtype(dtype)
+    if x.ndim == 0:
+        raise ValueError("cumulative_sum needs an array of at least one dimension")
+    if axis is None:
+        if x.ndim != 1:
+            raise ValueError("axis must be given for cumulative_sum of an array of more than one dimension")
+        axis = 0
+    axis = validate_axis(axis, x.ndim)
+    if include_initial:
+        raise NotImplementedError("cumulative_sum with include_initial=True is not supported: its "
+                                  "shape does not fit the regular chunk grid")
+    if dtype in (float32, float64):
+        value_dtype = dtype
+    else:
+        value_dtype = uint64 if dtype in _unsigned_integer_dtypes else int64
+    if x.size == 0:
+        from .creation_functions import empty
+
+        return empty(x.shape, dtype=dtype, chunks=x.chunks, spec=x.spec)
+    result = scan(astype(x, value_dtype, copy=False), axis)
+    return astype(result, dtype, copy=False)
 
 
 def _var_std(x, axis, correction, keepdims, use_new_impl, sqrt):

@@ -253,6 +253,7 @@ def general_blockwise(func, block_function, *arrays, shape, dtype, chunks, targe
     extra_source_arrays = kwargs.pop("extra_source_arrays", [])
     source_arrays = list(arrays) + list(extra_source_arrays)
     extra_projected_mem = kwargs.pop("extra_projected_mem", 0)
+    fusable = kwargs.pop("fusable", True)
     name = gensym()
     spec = check_array_specs(arrays)
     if target_store is None:
@@ -262,7 +263,7 @@ def general_blockwise(func, block_function, *arrays, shape, dtype, chunks, targe
         program, block_function, *zargs, allowed_mem=spec.allowed_mem,
         reserved_mem=spec.reserved_mem, extra_projected_mem=extra_projected_mem,
         target_store=target_store, shape=shape, dtype=dtype, chunks=chunks, in_names=in_names,
-        extra_func_kwargs=extra_func_kwargs)
+        extra_func_kwargs=extra_func_kwargs, fusable=fusable)
     if isinstance(op.target_array, DeviceArray):
         op.target_array.name = name
     plan = Plan._new(name, "blockwise", op.target_array, op, False, *source_arrays)
@@ -750,6 +751,70 @@ def reduction_new(x: "Array", func, combine_func=None, aggegrate_func=None, axis
     from ..array_api import astype
 
     return astype(result, dtype, copy=False)
+
+
+# ------------------------------------------------------------------ scans
+
+
+class _scan_block_function:
+    """Output block ``b`` of a scan with carry reads block ``b`` of the values
+    and the one carry chunk that holds the carry planes of ``b``'s row of
+    blocks along ``axis`` (coordinate 0 there)."""
+
+    def __init__(self, x_name, carry_name, axis):
+        self.x_name, self.carry_name, self.axis = x_name, carry_name, axis
+
+    def __call__(self, out_key):
+        coords = tuple(out_key[1:])
+        carry = coords[:self.axis] + (0,) + coords[self.axis + 1:]
+        return [(self.x_name,) + coords, (self.carry_name,) + carry]
+
+
+def scan(x: "Array", axis: int) -> "Array":
+    """Prefix sums of ``x`` along ``axis``, same shape, chunks and dtype.
+    ``x.dtype`` is one of the scan value types (float32, float64, int64,
+    uint64); floats accumulate in float64 (``ir.scan_acc_dtype``).
+
+    One block along ``axis``: one scan op.  ``nb`` blocks: per-chunk totals
+    (the first step of ``reduction``), merged so that the ``nb`` totals along
+    ``axis`` form one chunk, their exclusive prefix -- the carry of every
+    block -- and a scan of each chunk of ``x`` that starts from its carry
+    plane.  Every task reads whole chunks only and none reads a whole axis of
+    ``x``; the merged totals must fit ``allowed_mem``."""
+    from ..chunkfuncs import NumpyReduction
+
+    dtype = np.dtype(x.dtype)
+    acc = ir.scan_acc_dtype(dtype)
+    inds = tuple(range(x.ndim))
+    nb = x.numblocks[axis]
+    if nb == 1:
+        return blockwise(ir.ScanProgram(axis=axis, dtype=dtype), inds, x, inds, dtype=dtype,
+                         fusable=False)
+    spec = x.spec
+    totals_chunksize = tuple(1 if i == axis else c for i, c in enumerate(x.chunksize))
+    merged_chunksize = tuple(nb if i == axis else c for i, c in enumerate(x.chunksize))
+    merged_mem = chunk_memory(acc, merged_chunksize)
+    x_mem = chunk_memory(dtype, x.chunksize)
+    # the merge reads totals chunks into one merged chunk, the carry op reads
+    # and writes a merged chunk, the last op reads one next to its two chunks
+    # of x (a compressed and an uncompressed copy of each, as blockwise counts)
+    need = spec.reserved_mem + builtins.max(
+        2 * chunk_memory(acc, totals_chunksize) + 2 * merged_mem, 4 * merged_mem, 2 * merged_mem + 4 * x_mem)
+    if need > spec.allowed_mem:
+        raise ValueError(
+            f"Not enough memory for cumulative_sum. Increase allowed_mem ({spec.allowed_mem}) "
+            "or decrease chunk size")
+    sums = blockwise(NumpyReduction("sum", "sum").program(x.ndim, dtype, (axis,), keepdims=True, dtype=acc),
+                     inds, x, inds, dtype=acc, adjust_chunks={axis: (1,) * nb})
+    merged = merge_chunks(sums, merged_chunksize)
+    carry = blockwise(ir.ScanProgram(axis=axis, exclusive=True, dtype=acc), inds, merged, inds,
+                      dtype=acc, fusable=False)
+    # the carry chunk is an array argument, so the projected memory of the op
+    # already holds its two copies: no extra_projected_mem on top
+    return general_blockwise(ir.ScanProgram(axis=axis, carry=True, dtype=dtype, nargs=2),
+                             _scan_block_function(x.name, carry.name, axis), x, carry,
+                             shape=x.shape, dtype=dtype, chunks=x.chunks, extra_projected_mem=0,
+                             fusable=False)
 
 
 def _normalize_split_every(split_every, axis):

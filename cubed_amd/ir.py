@@ -418,6 +418,31 @@ class TensordotProgram(Program):
 
 
 @dataclass(frozen=True, eq=False)
+class ScanProgram(Program):
+    """Per task: the prefix sum of one chunk of argument 0 along ``axis``
+    (cumulative_sum).  ``dtype`` is the value type of input and output --
+    float32, float64, int64 or uint64; floats accumulate in float64, integers
+    wrap.  ``exclusive``: element i gets the sum of the elements before it.
+    ``carry``: argument 1 is a chunk holding, along ``axis``, one plane per
+    block of argument 0 -- the sum of everything before that block, in the
+    accumulator type -- and the task starts from the plane of its own block.
+    Not an expression program: the fusing rewrites leave it alone and it is
+    never fused with its producers or consumers."""
+    axis: int = 0
+    exclusive: bool = False
+    carry: bool = False
+    dtype: np.dtype = np.dtype("float64")
+    nargs: int = 1
+    name: str = "scan"
+
+
+def scan_acc_dtype(dtype) -> np.dtype:
+    """Accumulator (and carry) type of a scan over values of ``dtype``."""
+    dtype = np.dtype(dtype)
+    return np.dtype(np.float64) if dtype.kind == "f" else dtype
+
+
+@dataclass(frozen=True, eq=False)
 class GemmThenProgram(Program):
     """A chunk GEMM fused (by the DAG optimizer) with the program that
     consumes its output chunk: the executor runs the GEMM into the GEMM op's

@@ -317,6 +317,80 @@ class CopyLaunch:
                   "cubed_copy_boxes")
 
 
+# ------------------------------------------------------------------ scans
+
+
+def scan_vtype(dtype) -> int:
+    dtype = np.dtype(dtype)
+    if dtype == np.float32:
+        return V_F32
+    if dtype == np.float64:
+        return V_F64
+    if dtype in (np.dtype(np.int64), np.dtype(np.uint64)):
+        return V_I64
+    raise LoweringError(f"scan of {dtype} values is not lowered (float32, float64, int64, uint64)")
+
+
+def scan_task(src: ArrView, dst: ArrView, axis: int, carry: Optional[ArrView] = None, plane: int = 0):
+    """One nat.SCAN_TASK_DTYPE row: the compact C-ordered chunk views ``src``
+    and ``dst`` (equal extents) as (outer, n, inner) around ``axis``.
+    ``carry``: the view of the carry chunk -- the extents of ``src`` except
+    along ``axis``, where it holds one plane per block -- of which the task
+    starts from plane ``plane``."""
+    ext = list(src.extent)
+    if list(dst.extent) != ext:
+        raise LoweringError(f"scan chunk extents differ: {ext} -> {list(dst.extent)}")
+    outer, n, inner = math.prod(ext[:axis]), ext[axis], math.prod(ext[axis + 1:])
+    for v in (src, dst):
+        if list(v.stride) != list(c_strides(ext)):
+            raise LoweringError("scan chunks must be compact and C-ordered")
+    row = np.zeros((), dtype=nat.SCAN_TASK_DTYPE)
+    row["src_base"], row["dst_base"] = src.base, dst.base
+    row["outer"], row["n"], row["inner"] = outer, n, inner
+    row["src_outer_stride"] = row["dst_outer_stride"] = n * inner
+    row["src_n_stride"] = row["dst_n_stride"] = inner
+    if carry is not None:
+        cext = list(carry.extent)
+        if cext[:axis] != ext[:axis] or cext[axis + 1:] != ext[axis + 1:] or not 0 <= plane < cext[axis] \
+                or list(carry.stride) != list(c_strides(cext)):
+            raise LoweringError(f"carry chunk of extent {cext} does not match a scan chunk of extent {ext}")
+        row["carry_base"] = carry.base + plane * inner * carry.dtype.itemsize
+        row["carry_outer_stride"] = cext[axis] * inner
+    return row
+
+
+class ScanLaunch:
+    """One cubed_scan_chunks launch: a device table of scan tasks (one per
+    output chunk).  The kernel and its lane width are chosen once for the
+    whole table, on the host (cubed_scan_path).  ``sink``: the list of
+    buffers the cache entry being built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, vtype: int, exclusive: bool, device, sink=None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.vtype = vtype
+        self.exclusive = bool(exclusive)
+        if self.ntasks == 0:
+            return
+        self.path = nat.scan_path(rows, vtype)
+        if self.path == nat.SCAN_ROWS:
+            self.work = int(rows["outer"].max())
+        else:
+            self.work = int((rows["outer"] * rows["inner"]).max())
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0:
+            return
+        nat.check(nat.lib().cubed_scan_chunks(self.table.data_ptr(), self.ntasks, self.vtype,
+                                              int(self.exclusive), self.path, self.work, stream),
+                  "cubed_scan_chunks")
+
+
 # ------------------------------------------------------------------ programs
 
 

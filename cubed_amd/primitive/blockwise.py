@@ -157,7 +157,10 @@ def general_blockwise(
 
 
 def is_fuse_candidate(op: PrimitiveOperation) -> bool:
-    return op.pipeline.function is apply_blockwise
+    # a scan is its own launch under every optimizer (the linear-chain fusion
+    # of simple_optimize_dag does not look at ``fusable``)
+    return op.pipeline.function is apply_blockwise and \
+        not isinstance(op.pipeline.config.function, ir.ScanProgram)
 
 
 def can_fuse_primitive_ops(op1: PrimitiveOperation, op2: PrimitiveOperation) -> bool:

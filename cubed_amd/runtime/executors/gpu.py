@@ -45,6 +45,7 @@ from ...lowering import (
     GemmLaunch,
     LoweringError,
     Lowerer,
+    ScanLaunch,
     _OffsetsSource,
     boxes_for_region,
     chunk_view,
@@ -393,7 +394,7 @@ class GpuDagExecutor(DagExecutor):
                     f"op {name}: {program.func!r} cannot run on the MI355X executor "
                     "(not expressible as a fused chunk program)")
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
-                                    ir.PerBlockProgram)):
+                                    ir.PerBlockProgram, ir.ScanProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -434,6 +435,9 @@ class GpuDagExecutor(DagExecutor):
             return out
         if self.world == 1:
             return self._lower_local(program, cfg, target, keys)
+        if isinstance(program, ir.ScanProgram):
+            raise LoweringError("cumulative_sum runs on one GPU only: its scan launches are not "
+                                f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
                 not any(isinstance(l, ir.Concat) for l in ir.leaves_of_program(program)):
@@ -585,6 +589,8 @@ class GpuDagExecutor(DagExecutor):
                 from ...split import split_launches
 
                 return split_launches(self, program, cfg, target, keys)
+        if isinstance(program, ir.ScanProgram):
+            return [self._lower_scan(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -708,6 +714,33 @@ class GpuDagExecutor(DagExecutor):
             tasks[i] = (target.chunk_addr(key), am, bn, bn, i, 1, ak, 0)
         return GemmLaunch(tasks, segs, ir.dtype_code(in_dt or target.dtype), ir.dtype_code(target.dtype),
                           self.device, self.zero_page())
+
+    def _lower_scan(self, program, cfg, target, keys):
+        """One scan task per output chunk (ir.ScanProgram): the chunk of
+        argument 0 with the output chunk's extent and, with a carry, the
+        plane of the task's own block inside the carry chunk."""
+        from ...lowering import scan_task, scan_vtype
+
+        vtype = scan_vtype(program.dtype)
+        axis = program.axis
+        if np.dtype(target.dtype) != np.dtype(program.dtype):
+            raise LoweringError(f"scan of {program.dtype} values into a {target.dtype} array")
+        rows = np.zeros(len(keys), dtype=nat.SCAN_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            views = []
+            for a, dt in zip(args, (program.dtype, ir.scan_acc_dtype(program.dtype))):
+                if not isinstance(a, tuple):
+                    raise LoweringError("a scan task reads whole single chunks only")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != np.dtype(dt):
+                    raise LoweringError(f"scan input {a[0]} is not a device array of {np.dtype(dt)}")
+                views.append(chunk_view(src, a[1:]))
+            if len(views) != (2 if program.carry else 1):
+                raise LoweringError(f"scan program with {len(views)} inputs")
+            rows[i] = scan_task(views[0], chunk_view(target, key), axis,
+                                views[1] if program.carry else None, key[axis])
+        return ScanLaunch(rows, vtype, program.exclusive, self.device, self._sink)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""

@@ -35,6 +35,9 @@
  *                           cubed/array_api/linear_algebra_functions.py
  *                           :35-78, :139-149 (numpy BLAS sgemm/dgemm per task
  *                           + a reduction over k).
+ *   cubed_scan_chunks    -> no reference interface: Array API cumulative_sum
+ *                           (2023.12) is not in v0.12.0; the semantics are
+ *                           numpy's cumsum along one axis of a chunk.
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -45,7 +48,7 @@
 extern "C" {
 #endif
 
-#define CUBED_ABI_VERSION 17
+#define CUBED_ABI_VERSION 18
 
 #define CUBED_MAX_DIMS 6   /* iteration dims of one task after coalescing   */
 #define CUBED_MAX_LEAVES 4 /* array/philox/const-array inputs of a program  */
@@ -377,6 +380,44 @@ typedef struct {
 int cubed_copy_boxes(const cubed_box_t* d_boxes, int64_t nboxes, int32_t ndim,
                      int32_t itemsize, int32_t path, int32_t lane_bytes,
                      int64_t work, int64_t row_bytes, void* stream);
+
+/* Prefix sums along one axis of a chunk (cumulative_sum, ABI 18).  A task is
+ * one chunk seen as (outer, n, inner) -- the dims before the scanned axis
+ * coalesced into outer, those after it into inner, whose stride is 1 -- and
+ * writes dst[o, i, j] = carry[o, j] + sum of src[o, 0..i, j] (exclusive:
+ * 0..i-1).  Values are f32, f64 or int64 (uint64 has the same bits under a
+ * wrapping add); the sum runs in f64 for both float types and in wrapping
+ * 64-bit integers otherwise, and the carry plane holds that accumulator type
+ * (f64 for f32 values).  carry_base 0 = start from zero.  Tasks are
+ * independent: no workgroup communicates with another one, so results are
+ * bit-identical from run to run. */
+typedef struct {
+  int64_t src_base, dst_base, carry_base;      /* device byte addresses; carry_base 0 = none */
+  int64_t outer, n, inner;                     /* elements */
+  int64_t src_outer_stride, src_n_stride;      /* elements; the inner stride is 1 */
+  int64_t dst_outer_stride, dst_n_stride;
+  int64_t carry_outer_stride;                  /* elements of the accumulator type */
+} cubed_scan_task_t;
+
+/* path: CUBED_SCAN_ROWS    -- every task has inner == 1 and n contiguous: one
+ *                             wave per row, tiles of 64 lanes x 4 elements;
+ *                             work = max rows (outer) of a task
+ *       CUBED_SCAN_COLS    -- one lane per (outer, inner) column walking n;
+ *                             work = max outer * inner of a task
+ *       CUBED_SCAN_COLS_V4 -- the same with 4 consecutive inner elements per
+ *                             lane: inner, every base and every stride of
+ *                             every task keep 16-byte (f32) / 32-byte (f64,
+ *                             int64) alignment */
+#define CUBED_SCAN_ROWS 0
+#define CUBED_SCAN_COLS 1
+#define CUBED_SCAN_COLS_V4 2
+/* Host only (no device call): the path a HOST copy of a task table takes, or a
+ * negative CUBED_E_* code for a malformed table. */
+int cubed_scan_path(const cubed_scan_task_t* tasks, int64_t ntasks, int32_t vtype);
+/* One launch over a DEVICE task table, with the path cubed_scan_path gave for
+ * its host copy. */
+int cubed_scan_chunks(const cubed_scan_task_t* d_tasks, int64_t ntasks, int32_t vtype,
+                      int32_t exclusive, int32_t path, int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
