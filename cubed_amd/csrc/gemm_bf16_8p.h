@@ -1,11 +1,12 @@
-// gemm_bf16_8p.h -- bf16 chained GEMM on the PACKED operands of
-// gemm_bf16_w4p.h with TWO waves per SIMD (round 6; included by
-// gemm_chain.hip after gemm_bf16_w4p.h).
+// gemm_bf16_8p.h -- the library's bf16 chained GEMM on the PACKED operands of
+// gemm_bf16_pack.h, TWO waves per SIMD (round 6; included by gemm_chain.hip
+// after gemm_bf16_pack.h; launched by cubed_gemm_chain_packed and
+// cubed_gemm_dist_gemm).
 //
-// w4p runs one wave per SIMD: that wave issues its own LDS fragment reads and
-// LDS-DMA staging between its MFMAs, 40 cycles per 32-cycle MFMA in its main
-// loop.  Here the 256 x 256 tile has 8 waves in two groups of 4 (one wave of
-// each group per SIMD), each wave owning 128 x 64 of the tile on
+// Its predecessor (w4p, round 5) ran one wave per SIMD: that wave issued its
+// own LDS fragment reads and LDS-DMA staging between its MFMAs, 40 cycles per
+// 32-cycle MFMA in its main loop.  Here the 256 x 256 tile has 8 waves in two
+// groups of 4 (one wave of each group per SIMD), each wave owning 128 x 64 on
 // v_mfma_f32_16x16x32_bf16 (32 accumulators of 16 x 16).  A wave's K tile (64
 // k) is four phases, one 64 x 32 quadrant each (16 MFMAs), and every phase is
 // a READ interval (this phase's fragments by ds_read_b128, one staging piece
@@ -17,7 +18,7 @@
 // LDS: a ring of 10 half-tile slots of 16 KiB (160 KiB).  Half-tile u = 4 t + h
 // of K tile t is A rows 128 h .. +127 (h = 0, 1) or B^T rows 128 (h - 2) .. +127
 // (h = 2, 3) -- 16 KiB of consecutive bytes of the packed block, already the
-// LDS image (w4p's slot swizzle is bank-conflict free for the 16-row
+// LDS image (the pack's slot swizzle is bank-conflict free for the 16-row
 // fragment reads too) -- in slot u mod 10.  Phase s stages half-tile s + 7:
 // the slot it overwrites held half-tile s - 3, whose last read was issued two
 // or more intervals earlier (A half 0: group 0's phase 4t + 2; B halves:
@@ -29,56 +30,48 @@
 // Reads per wave and K tile: phase 0 A sub-tile 0 (8 x b128) + B sub-tile 0
 // (4), phase 1 B sub-tile 1 (4), phase 2 A sub-tile 1 (8), phase 3 none (B
 // sub-tile 0 kept in registers).  Per output element: one f32 chain over K in
-// k order, 32 k per MFMA -- the same products and order as w4p / w4l
+// k order, 32 k per MFMA -- the same products and order as w4l
 // (bit-identical results are checked by the tests).
 #pragma once
 
 constexpr int E8_NSLOT = 10, E8_HALF = 16384, E8_LEAD = 7;
-constexpr int E8_ROUNDS = 512;  // VAR bit: round_wait / round_done around the K loop (counters at stamp_out)
 
-// Measured on config 5 (tools/gemm_8p_probe.hip, profiles/r06_gemm_bf16_8p*.log,
-// every arm bit-identical to w4p): the library form -- each phase's two
-// staging pieces issued AFTER its fragment reads, no s_setprio -- 89.9-90.8
-// ms (1410-1424 TF) against w4p's 97.6-98.4 in the same process.  VAR (probe
-// arms only): 1 = staging pieces before the reads (the first form, 94.5-97.0
-// ms), 2 = s_setprio(1) / (0) around every MFMA cluster (91.0-91.8), 4 =
-// group 1 at priority 1 for the whole loop (91.1).  Also measured and
-// dropped: phase 0 reading B before A (equal), the wait for K tile t + 1 in
+// Measured on config 5 (profiles/r06_gemm_bf16_8p*.log, every form
+// bit-identical to w4p): this form -- each phase's two staging pieces issued
+// AFTER its fragment reads, no s_setprio -- 89.9-90.8 ms (1410-1424 TF)
+// against w4p's 97.6-98.4 in the same process.  Measured and dropped: the
+// staging pieces before the reads (94.5-97.0 ms), s_setprio(1) / (0) around
+// every MFMA cluster (91.0-91.8), group 1 at priority 1 for the whole loop
+// (91.1), phase 0 reading B before A (equal), the wait for K tile t + 1 in
 // phase 2 with its B sub-tile 0 read in phase 3 (reads 8 / 4 / 8 / 4; 95.1-99.3
 // ms: the shorter lead of the last half-tile), phase 0's pieces split around
-// its B reads (99.6), tile groups of 2 / 8 / 16 rows (95.4 / 90.7 / 97.8).
-// Ablations (probe only, WRONG results): 8 = no staging in the K loop, 16 =
-// every half-tile staged from K tile 0's addresses (L2-resident fills), 32 =
-// no fragment reads in the K loop.  64 = the round-5 tile order (xcd_remap:
-// each XCD a contiguous range of the grouped order) instead of xcd_lockstep;
-// 128 = xcd_lockstep without the round-robin tail; E8_ROUNDS (512, the
-// 1-GPU library form) = round_wait / round_done around the K loop (probe:
-// + 1024 / 2048 = a round may start with 4 / 8 of the last one unfinished): 84.3-84.5
-// ms against 85.0-85.2 (profiles/r06_gemm_round_sync.log).  (A 4 x 2 arrangement of
-// the XCDs, 16 A + 16 B^T panels per round, ran 88.5-88.8 ms against 87.7-88.1:
-// commit "Probe: 4 x 2 XCD tile arrangement", profiles/r06_gemm_tile_order.log.)
-template <bool OUT_BF16, bool STAMP = false, int VAR = 0, int GM = 4>
+// its B reads (99.6), tile groups of 2 / 8 / 16 rows in place of 4 (95.4 /
+// 90.7 / 97.8).  Where the time goes: without staging in the K loop the launch
+// takes 59.1 ms, with every fill L2-resident 73.7, without fragment reads 65.3,
+// against 88.4 -- the fills that miss L2 cost ~15 ms
+// (profiles/r06_gemm_bf16_8p_abl.log).
+// Tile order: xcd_lockstep (its comment; profiles/r06_gemm_tile_order.log).
+// ROUNDS (the 1-GPU launch; counters = PACK_CTR_BYTES zeroed before it):
+// round_wait / round_done around the K loop, 84.3-84.5 ms against 85.0-85.2
+// (profiles/r06_gemm_round_sync.log).  The per-rank launch passes no
+// counters and ROUNDS = false.
+template <bool OUT_BF16, bool ROUNDS = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_t* __restrict__ tasks,
                                                       const char* __restrict__ PA, const char* __restrict__ PB,
-                                                      PackPlan pp, GemmGrid gg,
-                                                      unsigned long long* __restrict__ stamp_out) {
+                                                      PackPlan pp, GemmGrid gg, unsigned* __restrict__ counters) {
   __shared__ __attribute__((aligned(1024))) char lds_[E8_NSLOT * E8_HALF];
   CUBED_L char* lds = (CUBED_L char*)lds_;
   int64_t t0, m0, n0;
-  const int64_t lt = (VAR & 64)    ? xcd_remap(blockIdx.x, gridDim.x)
-                     : (VAR & 128) ? xcd_lockstep<false>(blockIdx.x, gridDim.x, GM * pp.TN, pp.TM / GM)
-                                   : xcd_lockstep(blockIdx.x, gridDim.x, GM * pp.TN, pp.TM / GM);
-  tile_of<HB_BM, HB_BN, GM>(lt, pp.TM, pp.TN, t0, m0, n0);
+  tile_of<HB_BM, HB_BN, 4>(xcd_lockstep(blockIdx.x, gridDim.x, 4 * pp.TN, pp.TM / 4), pp.TM, pp.TN, t0, m0, n0);
   const int64_t M = pp.M, N = pp.N;
-  unsigned* const rctr = (VAR & E8_ROUNDS) ? (unsigned*)stamp_out : nullptr;
   if (t0 != 0 || m0 >= M || n0 >= N) {
-    if constexpr ((VAR & E8_ROUNDS) != 0) round_done(rctr, blockIdx.x);
+    if constexpr (ROUNDS) round_done(counters, blockIdx.x);
     return;
   }
-  if constexpr ((VAR & E8_ROUNDS) != 0) round_wait(rctr, blockIdx.x, 32, (VAR & 1024) ? 4 : (VAR & 2048) ? 8 : 0);
+  if constexpr (ROUNDS) round_wait(counters, blockIdx.x, 32);
   const int ktl = (int)pp.KTL, nph = 4 * ktl;
   // the last K tile holds <= 32 live k: its second 32-k half is not
-  // multiplied (w4p's K loop stops at ceil(K / 32) steps too)
+  // multiplied (w4l's K loop stops at ceil(K / 32) steps too)
   const bool half_last = (pp.K & 63) != 0 && (pp.K & 63) <= 32;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -90,8 +83,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
   const int64_t aks = pp.akstride;
   CUBED_L char* const dw = lds + (2 * w) * 1024;
   auto stage = [&](int u) __attribute__((always_inline)) {
-    if constexpr ((VAR & 8) != 0) return;
-    const int kt = (VAR & 16) ? 0 : u >> 2, h = u & 3;
+    const int kt = u >> 2, h = u & 3;
     const char* src = h < 2 ? sA + kt * aks + h * E8_HALF : sB + (int64_t)kt * 32768 + (h - 2) * E8_HALF;
     CUBED_L char* d = dw + (u % E8_NSLOT) * E8_HALF;
     glds16(src, d);
@@ -117,7 +109,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
     return *(const CUBED_L bf16x8*)(base + off);
   };
   auto read_a = [&](int t, int qm) __attribute__((always_inline)) {
-    if constexpr ((VAR & 32) != 0) return;
     CUBED_L const char* base = lds + ((4 * t + g) % E8_NSLOT) * E8_HALF;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -125,7 +116,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
       for (int kq = 0; kq < 2; ++kq) a[mt][kq] = rd(base, lo[kq] + (qm * 64 + mt * 16) * 128);
   };
   auto read_b = [&](int t, int qn, bf16x8 (&b)[2][2]) __attribute__((always_inline)) {
-    if constexpr ((VAR & 32) != 0) return;
     CUBED_L const char* base = lds + ((4 * t + 2 + hb) % E8_NSLOT) * E8_HALF + bcol;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
@@ -150,13 +140,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  auto mfma_begin = []() __attribute__((always_inline)) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr ((VAR & 2) != 0) __builtin_amdgcn_s_setprio(1);
-  };
-  auto mfma_end = []() __attribute__((always_inline)) {
-    if constexpr ((VAR & 2) != 0) __builtin_amdgcn_s_setprio(0);
-  };
+  // this phase's fragments have landed (opens every MFMA interval)
+  auto reads_landed = []() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
 
   // prologue: half-tiles 0 .. 6 staged, K tile 0 (halves 0 .. 3) waited
   for (int u = 0; u < E8_LEAD && u < nph; ++u) stage(u);
@@ -168,43 +153,32 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
   }
   barrier();
   if (g == 1) barrier();  // group 1 runs one interval behind group 0
-  if constexpr ((VAR & 4) != 0) {
-    if (g == 1) __builtin_amdgcn_s_setprio(1);
-  }
 
-  unsigned long long c0 = 0, c1 = 0;
-  if constexpr (STAMP) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c0)::"memory");
   // one K tile: four phases (the last K tile may multiply 32 k only)
   auto ktile = [&](int t, auto Half) __attribute__((always_inline)) {
     constexpr bool half = decltype(Half)::value;
     const int s = 4 * t;
     // phase 0: A sub-tile 0 + B sub-tile 0, quadrant (0, 0)
-    if ((VAR & 1) && s + E8_LEAD < nph) stage(s + E8_LEAD);
     read_a(t, 0);
     read_b(t, 0, b0);
-    if (!(VAR & 1) && s + E8_LEAD < nph) stage(s + E8_LEAD);
+    if (s + E8_LEAD < nph) stage(s + E8_LEAD);
     barrier();
-    mfma_begin();
+    reads_landed();
     quad(0, 0, b0, half);
-    mfma_end();
     barrier();
     // phase 1: B sub-tile 1, quadrant (0, 1)
-    if ((VAR & 1) && s + 1 + E8_LEAD < nph) stage(s + 1 + E8_LEAD);
     read_b(t, 1, b1);
-    if (!(VAR & 1) && s + 1 + E8_LEAD < nph) stage(s + 1 + E8_LEAD);
+    if (s + 1 + E8_LEAD < nph) stage(s + 1 + E8_LEAD);
     barrier();
-    mfma_begin();
+    reads_landed();
     quad(0, 1, b1, half);
-    mfma_end();
     barrier();
     // phase 2: A sub-tile 1, quadrant (1, 1)
-    if ((VAR & 1) && s + 2 + E8_LEAD < nph) stage(s + 2 + E8_LEAD);
     read_a(t, 1);
-    if (!(VAR & 1) && s + 2 + E8_LEAD < nph) stage(s + 2 + E8_LEAD);
+    if (s + 2 + E8_LEAD < nph) stage(s + 2 + E8_LEAD);
     barrier();
-    mfma_begin();
+    reads_landed();
     quad(1, 1, b1, half);
-    mfma_end();
     barrier();
     // phase 3: K tile t + 1 complete (this wave's pieces; every wave waits
     // before the barrier K tile t + 1's first readers pass), quadrant (1, 0)
@@ -214,9 +188,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (s + 3 + E8_LEAD < nph) stage(s + 3 + E8_LEAD);
     barrier();
-    mfma_begin();
+    reads_landed();
     quad(1, 0, b0, half);
-    mfma_end();
     barrier();
   };
   for (int t = 0; t + 1 < ktl; ++t) ktile(t, std::false_type{});
@@ -225,17 +198,11 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_8p(const cubed_gemm_chain_
   else
     ktile(ktl - 1, std::false_type{});
   if (g == 0) barrier();  // the same barrier count in both groups
-  if constexpr ((VAR & E8_ROUNDS) != 0) round_done(rctr, blockIdx.x);
-  if constexpr (STAMP) {
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c1)::"memory");
-    if (lane == 0) {
-      stamp_out[(blockIdx.x * 8 + w) * 2] = c1 - c0;
-      stamp_out[(blockIdx.x * 8 + w) * 2 + 1] = (unsigned long long)nph;
-    }
-  }
+  if constexpr (ROUNDS) round_done(counters, blockIdx.x);
 
   // epilogue: accumulator (mi, ni) register i = row 128 g + 16 mi + 4 (lane >>
-  // 4) + i, column 64 wc + 16 ni + (lane & 15); chunk selects as w4p's
+  // 4) + i, column 64 wc + 16 ni + (lane & 15); each element's chunk (of the
+  // at most four the tile touches) and its offset inside it
   const GridTile gt = grid_tile(tasks, gg, m0, n0);
   const cubed_gemm_chain_t* __restrict__ T = gt.T;
   const bool accum = T->accumulate != 0;

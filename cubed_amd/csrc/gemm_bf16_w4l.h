@@ -1,13 +1,14 @@
-// gemm_bf16_w4l.h -- the library's bf16 chained GEMM (round 5; included by
-// gemm_chain.hip): one wave per SIMD, 128 x 128 per wave on
-// v_mfma_f32_32x32x16_bf16, the K step hand-scheduled one filler per MFMA gap
-// (tools/gemm_bf16_w4i.h, tools/mfma_gap_probe.hip), A staged in FULL
+// gemm_bf16_w4l.h -- the library's bf16 chained GEMM on operands as stored
+// (round 5; included by gemm_chain.hip; launched by cubed_gemm_chain and
+// cubed_gemm_chain_grid when every segment has k >= 64): one wave per SIMD,
+// 128 x 128 per wave on v_mfma_f32_32x32x16_bf16, the K step hand-scheduled
+// one filler per MFMA gap (tools/mfma_gap_probe.hip), A staged in FULL
 // 128-byte lines.  Config 5 (40000^2 bf16, 64 chunk chains x 8 segments):
 // 1256-1258 TF vs 1108-1111 for the round-2..4 ping-pong kernel on the same
 // box, bit-identical results (profiles/r05_gemm_bf16_w4l.log).
 //
-// tools/gemm_w4i_probe.hip ablations (profiles/r05_gemm_bf16_w4i_ab.log):
-// the one-wave kernel with A staged 32 k deep runs 61-63 cycles per MFMA; holding A's staging
+// Why full lines (profiles/r05_gemm_bf16_w4i_ab.log): the one-wave kernel with
+// A staged 32 k deep runs 61-63 cycles per MFMA; holding A's staging
 // addresses still (B real) gives 42, holding B's (A real) 61 -- A's staging
 // is the cost.  A was staged 32 k at a time: every row a 64-B HALF line,
 // each global_load_lds piece 16 rows x 64 B (cdna_hip_programming.md:
@@ -43,31 +44,26 @@ __device__ __forceinline__ void wl_seq(F&& f) {
   wl_seq_(f, std::make_integer_sequence<int, N>{});
 }
 
-// STAMP: lane 0 of each wave stores the main loop's cycles (s_memtime) and
-// step count to stamp_out[(block * 4 + wave) * 2]
 // Requires every segment's k >= 64 (a 64-k A tile spans at most two
 // segments; cubed_gemm_chain checks) besides the MFMA path's rules.
-// ABL (tools/gemm_w4i_probe.hip ablations only, 0 in the library; results
-// wrong when nonzero): 1 no K-loop barrier, 2 no vmcnt wait in the K loop, 4 no fragment reads, 16 A
-// sources never advance, 32 B sources never advance.  STAMP: probe builds
-// store per-wave main-loop cycles to stamp_out (nullptr in the library).
 // GRID (cubed_gemm_chain_grid): 256 x 256 tiles over the WHOLE output of a
 // regular chunk grid, as k_gemm_bf16_chain<.., GRID>: a lane's A row / B
 // column / C element lies in chunk row I0 or I0+1 / column J0 or J0+1
 // (selected per lane where the sources are computed and in the epilogue),
 // so 5000-wide chunks are not each padded to 5120 (4.9 % of the MFMAs).
-template <bool OUT_BF16, int GM = 4, bool STAMP = false, int ABL = 0, bool GRID = false>
+// Tile groups of 4 rows: on the packed one-wave kernel with this K step, 1 /
+// 8 / 16 rows lost 1-5 % through the clock (profiles/r05_gemm_bf16_w4p_gm.log).
+template <bool OUT_BF16, bool GRID = false>
 __global__ __launch_bounds__(256, 1) void k_gemm_bf16_w4l(const cubed_gemm_chain_t* __restrict__ tasks,
                                                        const cubed_gemm_seg_t* __restrict__ segs,
                                                        int64_t tiles_m, int64_t tiles_n,
-                                                       const char* __restrict__ zero, GemmGrid gg,
-                                                       unsigned long long* __restrict__ stamp_out) {
+                                                       const char* __restrict__ zero, GemmGrid gg) {
   __shared__ __attribute__((aligned(1024))) char lds_[WL_LDS];
   CUBED_L char* lds = (CUBED_L char*)lds_;
   CUBED_L char* ldsA = lds;
   CUBED_L char* ldsB = lds + WL_NA * WL_ATILE;
   int64_t t, m0, n0;
-  tile_of<HB_BM, HB_BN, GM>(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, t, m0, n0);
+  tile_of<HB_BM, HB_BN, 4>(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, t, m0, n0);
   GridTile gt{0, 0, 0, 0, tasks + t, tasks + t, tasks + t};
   if constexpr (GRID) gt = grid_tile(tasks, gg, m0, n0);
   const cubed_gemm_chain_t* __restrict__ T = gt.T;
@@ -275,11 +271,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_bf16_w4l(const cubed_gemm_chain
     if (((p + 1) & 1) == 0 && ta < ntile) {
       const int32_t k0 = (int32_t)(ta * 64);
       if (wa.inc_ok && k0 + 64 <= wa.ke) {
-        if constexpr (!(ABL & 16)) {
 #pragma unroll
-          for (int i = 0; i < 8; ++i) stA[i] += 128;
-        }
-      } else if (!(ABL & 16) || k0 == 0) {
+        for (int i = 0; i < 8; ++i) stA[i] += 128;
+      } else {
         stageA_full(k0);
       }
       advance(wa, k0, 64, dsI);
@@ -288,11 +282,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_bf16_w4l(const cubed_gemm_chain
       const int32_t k0 = (int32_t)((p + 4) * HB_BK);
       if (wb.inc_ok && k0 + HB_BK <= wb.ke) {
         const uint64_t dB = (uint64_t)(HB_BK * wb.cur.ldb2), dBh = (uint64_t)(HB_BK * wb.hi.ldb2);
-        if constexpr (!(ABL & 32)) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) stB[i] += hB[i] ? dBh : dB;
-        }
-      } else if (!(ABL & 32) || k0 == 0) {
+        for (int i = 0; i < 4; ++i) stB[i] += hB[i] ? dBh : dB;
+      } else {
         stageB_full(k0);
       }
       advance(wb, k0, HB_BK, dsJ);
@@ -304,9 +296,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_bf16_w4l(const cubed_gemm_chain
   // fragments into Y; pieces 0-3: A part q of tile (p+5)>>1, 4-7: B of step p+4
   auto full_step = [&](int64_t p, const Frags& X, Frags& Y, auto Q) __attribute__((always_inline)) {
     constexpr int q = decltype(Q)::value;  // (p + 1) & 1, static in the unrolled loop
-    if constexpr (!(ABL & 2)) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(ABL & 1)) __builtin_amdgcn_s_barrier();  // every wave: step p+1 landed, step p's slots read
+    __builtin_amdgcn_s_barrier();  // every wave: step p+1 landed, step p's slots read
     __builtin_amdgcn_sched_barrier(0);
     set_bases(p + 1);
     const int ta = (int)((p + 5) >> 1);
@@ -317,29 +309,31 @@ __global__ __launch_bounds__(256, 1) void k_gemm_bf16_w4l(const cubed_gemm_chain
     bool incA = false;
     if constexpr (q == 0) {
       incA = wa.inc_ok && kA + 64 <= wa.ke;
-      if (!incA && (!(ABL & 16) || kA == 0)) stageA_full(kA);
+      if (!incA) stageA_full(kA);
     }
     const bool incB = wb.inc_ok && kB + HB_BK <= wb.ke;
-    if (!incB && (!(ABL & 32) || kB == 0)) stageB_full(kB);
+    if (!incB) stageB_full(kB);
     const uint64_t dB = (uint64_t)(HB_BK * wb.cur.ldb2), dBh = (uint64_t)(HB_BK * wb.hi.ldb2);
     __builtin_amdgcn_sched_barrier(0);
     wl_seq<32>([&](auto G) __attribute__((always_inline)) {
       constexpr int g = decltype(G)::value, r = g & 3, i = g >> 2;
       mfma(G, X, acc);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (r == 0) { if constexpr (!(ABL & 4)) read_a(std::integral_constant<int, i>{}, Y, lb); }
-      else if constexpr (r == 1) {
-        if constexpr (!(ABL & 4)) read_b(std::integral_constant<int, 2 * i>{}, Y, lb);
+      if constexpr (r == 0) {
+        read_a(std::integral_constant<int, i>{}, Y, lb);
+      } else if constexpr (r == 1) {
+        read_b(std::integral_constant<int, 2 * i>{}, Y, lb);
         if constexpr (i < 4) {
-          if constexpr (q == 0 && !(ABL & 16)) if (incA) { stA[i] += 128; stA[i + 4] += 128; }
+          if constexpr (q == 0) if (incA) { stA[i] += 128; stA[i + 4] += 128; }
         } else {
-          if constexpr (!(ABL & 32)) if (incB) stB[i - 4] += hB[i - 4] ? dBh : dB;
+          if (incB) stB[i - 4] += hB[i - 4] ? dBh : dB;
         }
-      }
-      else if constexpr (r == 2) {
+      } else if constexpr (r == 2) {
         if constexpr (i < 4) pieceA(4 * q + i, ta);
         else pieceB(i - 4, p + 4);
-      } else { if constexpr (!(ABL & 4)) read_b(std::integral_constant<int, 2 * i + 1>{}, Y, lb); }
+      } else {
+        read_b(std::integral_constant<int, 2 * i + 1>{}, Y, lb);
+      }
       __builtin_amdgcn_sched_barrier(0);
     });
     if constexpr (q == 0) advance(wa, kA, 64, dsI);
@@ -440,18 +434,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_bf16_w4l(const cubed_gemm_chain
   }
   // steady state from step 1: odd p stages part 0 (q = (p+1)&1 = 0), even p part 1
   int64_t p = 1;
-  unsigned long long t0 = 0, t1 = 0;
-  if constexpr (STAMP) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
   for (; p + 2 < nst && ((p + 6) >> 1) < ntile && p + 5 < nst; p += 2) {
     full_step(p, f1, f0, std::integral_constant<int, 0>{});
     full_step(p + 1, f0, f1, std::integral_constant<int, 1>{});
-  }
-  if constexpr (STAMP) {
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
-    if (lane == 0) {
-      stamp_out[(blockIdx.x * 4 + w) * 2] = t1 - t0;
-      stamp_out[(blockIdx.x * 4 + w) * 2 + 1] = (unsigned long long)(p - 1);
-    }
   }
   // tail: f1 holds step p's fragments (p odd here)
   for (; p < nst; ++p) {

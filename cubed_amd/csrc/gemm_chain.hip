@@ -11,34 +11,63 @@
 // 2 x 51.2 GB of f32 written and re-read), and a per-chunk product is simply
 // a chain of one segment.
 //
-// Kernels:
-//   k_gemm_bf16_chain  bf16 x bf16 -> f32 accumulate (-> f32 / bf16 out) on
-//                      v_mfma_f32_16x16x32_bf16.  256 x 256 output tile per
-//                      512-thread workgroup (8 waves, 2 (M) x 4 (N), each
-//                      128 x 64 = 8 x 4 accumulators), K staged 32 deep
-//                      straight from HBM into LDS with global_load_lds
-//                      (16 B per lane) through a 4-slot ring: three K steps
-//                      in flight while the fourth feeds the MFMAs.  The two
-//                      wave rows run "ping-pong", one barrier apart: on each
-//                      SIMD one wave issues its 32 MFMAs while the other
-//                      reads the next step's fragments and issues the
-//                      staging loads.
-//                      A is staged k-contiguous [m][64] (XOR-swizzled 16-B
-//                      chunks, conflict-free ds_read_b128 fragments); B is
-//                      staged as it lies in HBM, [k][256] rows, and read
-//                      transposed by ds_read_b64_tr_b16 (no transpose pass).
-//                      A segment boundary inside a K tile is a per-lane
-//                      pointer select; rows/cols past the chunk edge are
-//                      clamped (results discarded), k past the chain's end
-//                      reads a zero page.
+// Dispatch (host half of this file).  "MFMA shapes" = cubed_gemm_chain_path
+// says CUBED_GEMM_MFMA: bf16 -> f32 / bf16 or f32 -> f32, every segment's k
+// >= 32, k / lda / ldb / n multiples of 16 bytes, 16-B aligned operands, and
+// (bf16) n >= 8.  "k64" = every segment of every task has k >= 64.  All MFMA
+// kernels work on 256 x 256 output tiles and give bit-identical results for
+// one dtype (every element one f32 chain over K in k order; the tests check).
+//
+//   cubed_gemm_chain         each task tiled on its own (padded to 256s)
+//     bf16, MFMA shapes, k64        k_gemm_bf16_w4l<out>         gemm_bf16_w4l.h
+//     bf16, MFMA shapes, else       k_gemm_bf16_chain<out>       this file
+//     f32, MFMA shapes              k_gemm_f32_chain<false>      this file
+//     anything else (f64, int64,    k_gemm_any_chain<in, acc>    this file
+//       ragged shapes, CUBED_GEMM_ANY asked for)
+//   cubed_gemm_chain_grid    tasks = a regular ti x tj chunk grid of one
+//                            output (cubed_gemm_grid_check), tiles over the
+//                            whole matrix; MFMA shapes required
+//     bf16, k64                     k_gemm_bf16_w4l<out, true>
+//     bf16, else                    k_gemm_bf16_chain<out, true>
+//     f32                           k_gemm_f32_chain<true>
+//   cubed_gemm_chain_packed  the grid's tasks are ONE chunked product
+//                            (pack_plan); operands rewritten into the LDS
+//                            image first, workspace of cubed_gemm_pack_bytes
+//     bf16   k_pack_a, k_pack_bt (gemm_bf16_pack.h), counters zeroed, then
+//            k_gemm_bf16_8p<out, true>                           gemm_bf16_8p.h
+//     f32    k_pack_a_f32, k_pack_b_f32, k_gemm_f32_w4p          gemm_f32_w4p.h
+//   cubed_gemm_dist_pack_a   k blocks [kt0, kt1) of the k-major A image all
+//                            ranks share: k_pack_a / k_pack_a_f32
+//   cubed_gemm_dist_pack_b   the rank's own B columns: k_pack_bt / k_pack_b_f32
+//   cubed_gemm_dist_gemm     the rank's product from the two:
+//     bf16   k_gemm_bf16_8p<out, false> (no round counters)
+//     f32    k_gemm_f32_w4p
+//
+// Each kernel's comment says what it does, why that form won and what was
+// measured and dropped (logs under profiles/; the probes that produced them
+// are listed in tools/RETIRED.md).  In short:
+//   k_gemm_bf16_w4l    operands as stored; one wave per SIMD, 128 x 128 per
+//                      wave on v_mfma_f32_32x32x16_bf16, A staged in full
+//                      128-B lines 64 k at a time (hence k64).
+//   k_gemm_bf16_chain  operands as stored, any MFMA shape; 8 waves (2 x 4,
+//                      128 x 64 each) on v_mfma_f32_16x16x32_bf16, K staged 32
+//                      deep by global_load_lds through a 4-slot ring, the two
+//                      wave rows "ping-pong" one barrier apart.  A is staged
+//                      k-contiguous [m][64 B] (XOR-swizzled 16-B chunks); B as
+//                      it lies in HBM and read transposed by
+//                      ds_read_b64_tr_b16.  A segment boundary inside a K step
+//                      is a per-lane pointer select; rows / columns past the
+//                      chunk edge are clamped (results discarded), k past the
+//                      chain's end reads a zero page.
+//   k_gemm_bf16_8p     packed operands; two waves per SIMD, four phases per
+//                      64-k tile, no segment or edge logic in the K loop.
 //   k_gemm_f32_chain   f32 on v_mfma_f32_32x32x2_f32 (exact f32 products, f32
-//                      accumulate): the bf16 kernel's 256 x 256 tile and
-//                      global_load_lds ring, K 16 deep per step, ds_read_b128
-//                      fragments for both operands (k and column
-//                      permutations, see the kernel).
-//   k_gemm_any_chain   any dtype (f64 / int64 / ragged bf16 or f32 shapes):
-//                      64 x 64 tiles of scalar FMAs, every element bounds-
-//                      checked.  Correctness path, not a fast path.
+//                      accumulate): the same tile and ring, K 16 deep per
+//                      step, one barrier per step, ds_read_b128 fragments for
+//                      both operands (k and column permutations).
+//   k_gemm_f32_w4p     packed operands; one wave per SIMD, 128 x 128 per wave.
+//   k_gemm_any_chain   any dtype: 64 x 64 tiles of scalar FMAs, every element
+//                      bounds-checked.  Correctness path, not a fast path.
 #include "common.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -65,35 +94,37 @@ __device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nblk) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
 }
 
-// (probe) the 8 XCDs on different row groups of GM tile rows (per_group
-// tiles each) but at the same columns: XCD x's i-th workgroup takes group x + 8
-// (i / per_group) while every XCD has whole groups left, then a contiguous
-// share of the rest (as xcd_remap) -- B column panels read by all eight XCDs
-// at about the same time, for the memory-side cache to serve.
-// The rest (rr_tail): runs of 32 tiles of the grouped order (GM x 8 of one
+// Block order of the packed GEMMs: the 8 XCDs on different row groups of GM
+// tile rows (per_group tiles each) but at the same columns.  XCD x's i-th
+// workgroup takes group x + 8 (i / per_group) while every XCD has whole groups
+// left, so B column panels are read by all eight XCDs at about the same time,
+// for the memory-side cache to serve.
+// The rest (xcd_tail): runs of 32 tiles of the grouped order (GM x 8 of one
 // group) dealt round robin, so the eight XCDs work on neighbouring columns of
 // one row group (its A panels read by all eight together); the last < 256
-// tiles as contiguous shares.
-template <bool RR_TAIL = true>
+// tiles as contiguous shares (as xcd_remap).
+// bf16 88.1-90.4 ms against 89.8-92.4 for xcd_remap's contiguous ranges, f32
+// equal (profiles/r06_gemm_tile_order.log).  Measured and dropped: a 4 x 2
+// arrangement of the XCDs (88.5-88.8 against 87.7-88.1 ms, same log).
 __device__ __forceinline__ int64_t xcd_tail(int64_t x, int64_t j, int64_t S, int64_t base) {
-  if constexpr (RR_TAIL) {
+  {  // the runs dealt round robin
     const int64_t runs = (S >> 8) << 8 >> 5;  // whole rounds of 8 runs of 32
     if (j < runs * 4) return base + ((j >> 5) * 8 + x) * 32 + (j & 31);
     base += runs * 32;
     S -= runs * 32;
     j -= runs * 4;
   }
+  // the last < 256 tiles: contiguous shares
   const int64_t q = S >> 3, r = S & 7;
   return base + (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
 
-template <bool RR_TAIL = true>
 __device__ __forceinline__ int64_t xcd_lockstep(int64_t b, int64_t nblk, int64_t per_group, int64_t full_groups) {
   const int64_t main = (full_groups >> 3) * per_group;
   const int64_t x = b & 7, i = b >> 3;
   if (nblk < 8 || main == 0) return xcd_remap(b, nblk);
   if (i < main) return (x + 8 * (i / per_group)) * per_group + i % per_group;
-  return xcd_tail<RR_TAIL>(x, i - main, nblk - 8 * main, 8 * main);
+  return xcd_tail(x, i - main, nblk - 8 * main, 8 * main);
 }
 
 // Tile-round alignment (the 1-GPU packed bf16 GEMM): the i-th workgroup on an XCD (b & 7, local
@@ -101,12 +132,15 @@ __device__ __forceinline__ int64_t xcd_lockstep(int64_t b, int64_t nblk, int64_t
 // of earlier rounds of R (one per CU) have left their K loops, so a round's
 // tiles start their K walks together and share panel lines in L2; a timeout
 // only costs the alignment.  ctr: one uint32 per XCD, 128 B apart, zeroed
-// before the launch.
-__device__ __forceinline__ void round_wait(unsigned* ctr, int64_t b, int64_t R, int64_t slack = 0) {
+// before the launch.  bf16 84.3-84.5 ms against 85.0-85.2 without; the packed
+// f32 GEMM ran slower with it (882.9-883.8 against 878.5-879.5 ms) and does
+// not use it; letting a round start with 4 or 8 tiles of the last one
+// unfinished gained nothing (profiles/r06_gemm_round_sync.log).
+__device__ __forceinline__ void round_wait(unsigned* ctr, int64_t b, int64_t R) {
   const int64_t i = b >> 3;
   if (i >= R) {
     if (threadIdx.x == 0) {
-      const unsigned need = (unsigned)((i / R) * R - slack);
+      const unsigned need = (unsigned)((i / R) * R);
       // ~1.5 us per poll: a few ms at most (a round's spread is tens of us)
       for (int it = 0; it < 2000; ++it) {
         if (__hip_atomic_load(ctr + (b & 7) * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need) break;
@@ -206,24 +240,27 @@ __device__ __forceinline__ void glds16(const char* src, CUBED_L char* dst) {
   __builtin_amdgcn_global_load_lds((const CUBED_G void*)(uintptr_t)src, (CUBED_L void*)dst, 16, 0, 0);
 }
 
-// ABL: ablation bits for tools/gemm_bf16_probe.hip only (0 in the library):
-// 1 = no K-loop staging, 2 = no B fragment reads, 4 = no A fragment reads,
-// 8 = no K-loop barrier; ping-pong only: 16 = no vmcnt wait in the K loop,
-// 32 = every K step staged from step 0's addresses (L2-resident), 1 = no
-// K-loop staging.  Any nonzero value computes wrong results.
-// PP: 0 = one barrier per step, 1 = ping-pong (the library's), 2 = ping-pong
-// with register staging (see the K loop).
-// NS: ring slots (each step p+NS-1 is staged while step p is consumed);
-// GM: tile rows per XCD tile group.
-template <bool OUT_BF16, int ABL = 0, int PP = 0, int NS = HB_NS, int GM = 4, bool GRID = false>
+// The bf16 kernel for chains with a segment shorter than 64 k (longer ones
+// take k_gemm_bf16_w4l): the two wave rows run "ping-pong", one barrier
+// apart (see the K loop): 1071.7 TF on config 5 against 1020.6 for one
+// barrier per step on the same ring (profiles/r02_gemm_bf16_variants.log).
+// Measured and dropped, all bit-identical: a 5-slot ring (1067.9 TF), tile
+// groups of 8 / 2 rows in place of 4 (1049.4 / 1056.2; same log), the staging
+// loads issued in the compute slot (1041.5-1045.4 against 1052.6-1058.0,
+// profiles/r03_gemm_bf16_cslot.log), scalar-base staging addresses
+// (1036.9-1038.9 against 1067.3-1077.9, profiles/r03_gemm_bf16_saddr.log),
+// and register staging (global_load_dwordx4 + ds_write_b128) in place of
+// LDS-DMA (the r03_gemm_* logs).
+template <bool OUT_BF16, bool GRID = false>
 __global__ __launch_bounds__(512, 2) void k_gemm_bf16_chain(const cubed_gemm_chain_t* __restrict__ tasks,
                                                          const cubed_gemm_seg_t* __restrict__ segs,
                                                          int64_t tiles_m, int64_t tiles_n,
                                                          const char* __restrict__ zero, GemmGrid gg) {
-  __shared__ __attribute__((aligned(1024))) char lds_[(PP == 2 ? 2 : NS) * HB_STAGE];
+  constexpr int NS = HB_NS;
+  __shared__ __attribute__((aligned(1024))) char lds_[NS * HB_STAGE];
   CUBED_L char* lds = (CUBED_L char*)lds_;
   int64_t t, m0, n0;
-  tile_of<HB_BM, HB_BN, GM>(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, t, m0, n0);
+  tile_of<HB_BM, HB_BN, 4>(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, t, m0, n0);
   GridTile gt{0, 0, 0, 0, tasks + t, tasks + t, tasks + t};
   if constexpr (GRID) gt = grid_tile(tasks, gg, m0, n0);
   const cubed_gemm_chain_t* __restrict__ T = gt.T;
@@ -359,180 +396,70 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16_chain(const cubed_gemm_cha
   const int64_t nst = (KT + HB_BK - 1) / HB_BK;
   constexpr int D = NS - 1;  // steps staged ahead
   // prologue: steps 0 .. D-1 in flight (LDS-DMA schedules)
-  if constexpr (PP != 2)
-    for (int64_t p = 0; p < D && p < nst; ++p) stage(p * HB_BK, lds + p * HB_STAGE);
+  for (int64_t p = 0; p < D && p < nst; ++p) stage(p * HB_BK, lds + p * HB_STAGE);
   // retire this wave's loads of step q (4 per step; steps up to q + D - 1 issued)
+  static_assert(D == 3, "wait_step counts two younger steps");
   auto wait_step = [&](int64_t q) {
     int64_t younger = nst - 1 - q;
     if (younger > D - 1) younger = D - 1;
-    if (younger >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
-  static_assert(PP == 2 ? (NS >= 2 && NS <= 4) : (NS >= 3 && NS <= 5), "ring of 3..5 slots (PP 2: 2..4 register sets)");
   int rd = 0, wr_slot = D % NS;  // ring slots of steps p and p + D
-  if constexpr (PP == 2) {
-    // Ping-pong with REGISTER staging: global_load_dwordx4 into VGPRs, then
-    // ds_write_b128, instead of LDS-DMA (an LDS-DMA instruction costs its
-    // wave 60-185 issue cycles, MI355X_MICROARCH.md per-instruction
-    // constants).  LDS holds two slots: M(p) reads step p from slot p&1,
-    // writes step p+1 (loaded NS-1 memory slots earlier) into slot (p+1)&1
-    // and issues step p+NS's loads into the register set step p vacated.
-    // RAW: M(p)'s ds_writes retire (lgkmcnt(0)) before the barrier ending its
-    //   slot; step p+1 is read in M(p+1), which in both rows starts after
-    //   both rows' M(p) ended.
-    // WAR: slot (p+1)&1 last held step p-1, read in M(p-1), which ended in
-    //   both rows before either row's M(p) started.
-    constexpr int RD = NS;  // register sets: loads of RD steps in flight
-    u32x4 rs[RD][4];
-    int wdst[4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      wdst[i] = (2 * w + i) * 1024 + lane * 16;
-      wdst[2 + i] = HB_A + (2 * w + i) * 1024 + lane * 16;
-    }
-    auto gload = [&](int64_t k0, u32x4 (&dst)[4]) {
-      stage_addrs(k0, lds);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dst[i] = *(const CUBED_G u32x4*)(uintptr_t)st_src[i];
-    };
-    auto swrite = [&](CUBED_L char* buf, const u32x4 (&src)[4]) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *(CUBED_L u32x4*)(buf + wdst[i]) = src[i];
-    };
-#pragma unroll
-    for (int r = 0; r < RD; ++r)
-      if (r < nst) gload(r * HB_BK, rs[r]);
-    if (nst > 0) swrite(lds, rs[0]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 af[8];
-    for (int64_t p0 = 0; p0 < nst; p0 += RD) {
-#pragma unroll
-      for (int r = 0; r < RD; ++r) {
-        const int64_t p = p0 + r;
-        if (p >= nst) break;
-        // ---- M(p)
-        const CUBED_L char* bufc = lds + (p & 1) * HB_STAGE;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-          const uint32_t pb = (uint32_t)(uintptr_t)(bufc + offB[nb]);
-          s16x4 lo, hi;
-          asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(pb));
-          asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(hi) : "v"(pb));
-          bf[nb] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
-#pragma unroll
-        for (int mb = 0; mb < 8; ++mb) af[mb] = *(const CUBED_L bf16x8*)(bufc + offA + mb * 1024);
-        if (p + 1 < nst) swrite(lds + ((p + 1) & 1) * HB_STAGE, rs[(r + 1) % RD]);
-        if (p + RD < nst) gload((p + RD) * HB_BK, rs[r]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- C(p)
-#pragma unroll
-        for (int mb = 0; mb < 8; ++mb)
-#pragma unroll
-          for (int nb = 0; nb < 4; ++nb)
-            acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mb], bf[nb], acc[mb][nb], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (wr == 0) __builtin_amdgcn_s_barrier();  // same barrier count in both rows
-  } else if constexpr (PP == 1) {
-    // Ping-pong: the two wave rows (wr = 0, 1: one wave of each per SIMD)
-    // run one barrier-delimited slot apart, alternating a memory slot M(p)
-    // -- step p's fragments into registers, step p+3's global->LDS loads --
-    // and a compute slot C(p) of 32 MFMAs, so each SIMD's matrix core is fed
-    // by one wave while the other reads LDS.  Global slot 2p: row 0 in M(p),
-    // row 1 in C(p-1); slot 2p+1: row 0 in C(p), row 1 in M(p).
-    // RAW: every wave retires its step p+1 loads at the end of M(p) (slot 2p
-    //   or 2p+1), before the barrier ending slot 2p+1; step p+1 is read in
-    //   slot 2p+2 at the earliest.
-    // WAR: M(p) restages slot (p+3)%4 = step p-1's, whose last reader (row 1,
-    //   M(p-1), slot 2p-1) retired its reads (lgkmcnt(0)) before the barrier
-    //   ending slot 2p-1.
-    if (nst > 0) wait_step(0);
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 af[8];
-    for (int64_t p = 0; p < nst; ++p) {
-      // ---- M(p)
-      const CUBED_L char* bufc = lds + rd * HB_STAGE;
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb) {
-        const uint32_t pb = (uint32_t)(uintptr_t)(bufc + offB[nb]);
-        s16x4 lo, hi;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(pb));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(hi) : "v"(pb));
-        bf[nb] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
-#pragma unroll
-      for (int mb = 0; mb < 8; ++mb) af[mb] = *(const CUBED_L bf16x8*)(bufc + offA + mb * 1024);
-      if (!(ABL & 1) && p + D < nst) stage((ABL & 32) ? 0 : (p + D) * HB_BK, lds + wr_slot * HB_STAGE);
-      rd = rd + 1 == NS ? 0 : rd + 1;
-      wr_slot = wr_slot + 1 == NS ? 0 : wr_slot + 1;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(ABL & 16) && p + 1 < nst) wait_step(p + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- C(p)
-#pragma unroll
-      for (int mb = 0; mb < 8; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-          acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mb], bf[nb], acc[mb][nb], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (wr == 0) __builtin_amdgcn_s_barrier();  // same barrier count in both rows
-  } else
+  // Ping-pong: the two wave rows (wr = 0, 1: one wave of each per SIMD)
+  // run one barrier-delimited slot apart, alternating a memory slot M(p)
+  // -- step p's fragments into registers, step p+3's global->LDS loads --
+  // and a compute slot C(p) of 32 MFMAs, so each SIMD's matrix core is fed
+  // by one wave while the other reads LDS.  Global slot 2p: row 0 in M(p),
+  // row 1 in C(p-1); slot 2p+1: row 0 in C(p), row 1 in M(p).
+  // RAW: every wave retires its step p+1 loads at the end of M(p) (slot 2p
+  //   or 2p+1), before the barrier ending slot 2p+1; step p+1 is read in
+  //   slot 2p+2 at the earliest.
+  // WAR: M(p) restages slot (p+3)%4 = step p-1's, whose last reader (row 1,
+  //   M(p-1), slot 2p-1) retired its reads (lgkmcnt(0)) before the barrier
+  //   ending slot 2p-1.
+  if (nst > 0) wait_step(0);
+  __builtin_amdgcn_s_barrier();
+  if (wr == 1) __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  bf16x8 af[8];
   for (int64_t p = 0; p < nst; ++p) {
-    // this wave's loads of step p have landed once at most the younger
-    // steps' loads (4 per step) are outstanding
-    if (ABL & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else wait_step(p);
-    // every wave's step p landed; every wave finished reading step p-1's slot
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(ABL & 8)) __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (!(ABL & 1) && p + D < nst) stage((p + D) * HB_BK, lds + wr_slot * HB_STAGE);
-    const CUBED_L char* bufc = lds + rd * HB_STAGE;
-    rd = rd + 1 == NS ? 0 : rd + 1;
-    wr_slot = wr_slot + 1 == NS ? 0 : wr_slot + 1;
+    // ---- M(p)
     // B fragments by transposed reads.  Inline asm: the builtin has no memory
     // operand, so hipcc would put an s_waitcnt vmcnt(0) in front of it --
     // draining the three K steps in flight -- and the reads only touch slot
-    // p, which the vmcnt + barrier above already made visible.
+    // p, which the vmcnt + barrier before it already made visible.
+    const CUBED_L char* bufc = lds + rd * HB_STAGE;
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-      if ((ABL & 2) && p > 0) break;
       const uint32_t pb = (uint32_t)(uintptr_t)(bufc + offB[nb]);
       s16x4 lo, hi;
       asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(pb));
       asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(hi) : "v"(pb));
       bf[nb] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    // (s_setprio(1) around this MFMA cluster measured 1046 vs 1069 TF: not used)
 #pragma unroll
-    for (int mb = 0; mb < 8; ++mb) {
-      const bf16x8 af = (ABL & 4) ? bf[mb & 3] : *(const CUBED_L bf16x8*)(bufc + offA + mb * 1024);
+    for (int mb = 0; mb < 8; ++mb) af[mb] = *(const CUBED_L bf16x8*)(bufc + offA + mb * 1024);
+    if (p + D < nst) stage((p + D) * HB_BK, lds + wr_slot * HB_STAGE);
+    rd = rd + 1 == NS ? 0 : rd + 1;
+    wr_slot = wr_slot + 1 == NS ? 0 : wr_slot + 1;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (p + 1 < nst) wait_step(p + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- C(p)
+#pragma unroll
+    for (int mb = 0; mb < 8; ++mb)
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb)
-        acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[nb], acc[mb][nb], 0, 0, 0);
-    }
+        acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mb], bf[nb], acc[mb][nb], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
   }
+  if (wr == 0) __builtin_amdgcn_s_barrier();  // same barrier count in both rows
 
   // ---- epilogue: C/D map col = lane&15, row = (lane>>4)*4 + r
   const bool accum = T->accumulate != 0;
@@ -568,7 +495,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16_chain(const cubed_gemm_cha
 }
 
 #include "gemm_bf16_w4l.h"
-#include "gemm_bf16_w4p.h"
+#include "gemm_bf16_pack.h"
 #include "gemm_bf16_8p.h"
 
 // ------------------------------------------------------------------ f32 MFMA
@@ -592,27 +519,33 @@ __global__ __launch_bounds__(512, 2) void k_gemm_bf16_chain(const cubed_gemm_cha
 // LDS slot: A [256 rows][16 k] (64-B rows, 16-B chunk c of row r at
 // position c ^ ((r >> 2) & 3): conflict-free b128 reads) + B [16 k][256 n]
 // (1 KiB rows, as in HBM).
+//
+// The unpacked f32 kernel (per-chunk and grid forms; the packed one is
+// gemm_f32_w4p.h): 16-deep steps in a 4-slot ring, 129.6-130.0 TF on config
+// 5.  Measured and dropped: 32-deep steps in 2 slots (128.1-128.2 TF) and a
+// 3-slot ring (equal; profiles/r03_gemm_f32_variants.log), the bf16 kernel's
+// ping-pong schedule (121.4-121.8 TF, profiles/r03_gemm_f32_pingpong.log),
+// reading step p+1's first fragments under step p's last MFMAs (1.3 % slower,
+// profiles/r03_gemm_f32_prefetch.log) and tile groups of 8 rows (equal time
+// and fetch, profiles/r03_gemm_f32_group8.log).
 constexpr int HF_BM = 256, HF_BN = 256;
+constexpr int HF_BK = 16, HF_NS = 4;  // K depth of one ring slot; ring slots
 
-// BK: K depth of one ring slot (16 or 32); NS: ring slots.  A slot holds A
-// [256 rows][BK k] (BK*4-byte rows, CPR = BK/4 16-B chunks, chunk c of row
-// r at position c ^ swz(r): conflict-free b128 reads) + B [BK k][256 n]
-// (1 KiB rows, as in HBM).
-template <int BK, int NS, bool PP = false, bool GRID = false>
+template <bool GRID = false>
 __global__ __launch_bounds__(512, 2) void k_gemm_f32_chain(const cubed_gemm_chain_t* __restrict__ tasks,
                                                         const cubed_gemm_seg_t* __restrict__ segs,
                                                         int64_t tiles_m, int64_t tiles_n,
                                                         const char* __restrict__ zero, GemmGrid gg) {
-  static_assert(BK == 16 || BK == 32, "K step of 16 or 32");
+  constexpr int BK = HF_BK, NS = HF_NS;
   constexpr int SA = HF_BM * BK * 4, SB = BK * HF_BN * 4, STAGE = SA + SB;
-  constexpr int CPR = BK / 4;            // 16-B chunks per A row
-  constexpr int RPI = 1024 / (BK * 4);   // A rows per wave instruction (1 KiB)
-  constexpr int NA = HF_BM / RPI / 8;    // A loads per wave per step
-  constexpr int NB = BK / 8;             // B loads per wave per step
+  constexpr int CPR = BK / 4;            // 16-B chunks per A row (4)
+  constexpr int RPI = 1024 / (BK * 4);   // A rows per wave instruction (1 KiB: 16)
+  constexpr int NA = HF_BM / RPI / 8;    // A loads per wave per step (2)
+  constexpr int NB = BK / 8;             // B loads per wave per step (2)
   constexpr int LPS = NA + NB;           // vmcnt per step
-  constexpr int SWS = BK == 16 ? 2 : 1;  // swz(r) = (r >> SWS) & (CPR - 1)
-  constexpr int G = BK / 8;              // 8-deep k groups per step
-  static_assert(NS * STAGE <= 160 * 1024, "LDS");
+  constexpr int SWS = 2;                 // swz(r) = (r >> SWS) & (CPR - 1)
+  constexpr int G = BK / 8;              // 8-deep k groups per step (2)
+  static_assert(BK == 16 && NS * STAGE <= 160 * 1024, "swizzle and LDS budget are for 16-deep steps");
   __shared__ __attribute__((aligned(1024))) char lds_[NS * STAGE];
   CUBED_L char* lds = (CUBED_L char*)lds_;
   int64_t t, m0, n0;
@@ -755,51 +688,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_f32_chain(const cubed_gemm_chai
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   int rd = 0, wr_slot = D % NS;
-  if constexpr (PP) {
-    // Ping-pong (the bf16 kernel's schedule): wave rows 0-1 (w < 4) and 2-3
-    // run one barrier apart, alternating a memory slot M(p) -- step p's 12
-    // fragment reads into registers, step p+D's staging loads, the wait for
-    // step p+1 -- and a compute slot C(p) of 64 MFMAs, so on every SIMD one
-    // wave's MFMAs cover the other's LDS reads.  RAW / WAR as in
-    // k_gemm_bf16_chain (same ring).
-    const int half = w >> 2;
-    if (nst > 0) wait_step(0);
-    __builtin_amdgcn_s_barrier();
-    if (half == 1) __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 af[G][2], bq[G][4];
-    for (int64_t p = 0; p < nst; ++p) {
-      const CUBED_L char* bufc = lds + rd * STAGE;
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) af[g][rb] = *(const CUBED_L f32x4*)(bufc + offA[rb][g]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bq[g][j] = *(const CUBED_L f32x4*)(bufc + offB + (8 * g + j) * 1024);
-      }
-      if (p + D < nst) stage((p + D) * BK, lds + wr_slot * STAGE);
-      rd = rd + 1 == NS ? 0 : rd + 1;
-      wr_slot = wr_slot + 1 == NS ? 0 : wr_slot + 1;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (p + 1 < nst) wait_step(p + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              acc[rb][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][rb][j], bq[g][j][q], acc[rb][q], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (half == 0) __builtin_amdgcn_s_barrier();  // same barrier count in both halves
-  } else
   for (int64_t p = 0; p < nst; ++p) {
     // this wave's step p landed; then every wave's (barrier), and every wave
     // finished reading step p-1's slot (restaged below)
@@ -811,7 +699,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm_f32_chain(const cubed_gemm_chai
     const CUBED_L char* bufc = lds + rd * STAGE;
     rd = rd + 1 == NS ? 0 : rd + 1;
     wr_slot = wr_slot + 1 == NS ? 0 : wr_slot + 1;
-    // fragments of group g+1 are read while group g's 32 MFMAs run
+    // both k groups' fragments are issued before the 64 MFMAs: group 1's
+    // land while group 0's 32 MFMAs run
     f32x4 af[G][2], bq[G][4];
     auto read_group = [&](int g) {
 #pragma unroll
@@ -820,10 +709,10 @@ __global__ __launch_bounds__(512, 2) void k_gemm_f32_chain(const cubed_gemm_chai
       for (int j = 0; j < 4; ++j) bq[g][j] = *(const CUBED_L f32x4*)(bufc + offB + (8 * g + j) * 1024);
     };
     read_group(0);
-    if constexpr (G > 1) read_group(1);
+    read_group(1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < G; ++g)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -831,12 +720,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm_f32_chain(const cubed_gemm_chai
 #pragma unroll
           for (int q = 0; q < 4; ++q)
             acc[rb][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][rb][j], bq[g][j][q], acc[rb][q], 0, 0, 0);
-      if (g + 2 < G) {
-        __builtin_amdgcn_sched_barrier(0);
-        read_group(g + 2);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
   }
 
   // ---- epilogue: accumulator (rb, q) register r = row wm + 32 rb + (r&3) +
@@ -949,6 +832,34 @@ int fail(const char* m) {
 
 bool aligned16(int64_t x) { return (x & 15) == 0; }
 
+// after an entry point's launches: the first launch error, if any
+int launch_status() {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e));
+  return (int)e;
+}
+
+// every segment of these tasks spans a 64-k A tile (k_gemm_bf16_w4l's rule)
+bool all_segments_k64(const cubed_gemm_chain_t* tasks, int64_t ntasks, const cubed_gemm_seg_t* segs) {
+  for (int64_t t = 0; t < ntasks; ++t)
+    for (int64_t i = tasks[t].seg0; i < tasks[t].seg0 + tasks[t].nseg; ++i)
+      if (segs[i].k < 64) return false;
+  return true;
+}
+
+// the whole output of a regular ti x tj chunk grid (cubed_gemm_grid_check)
+GemmGrid grid_of(const cubed_gemm_chain_t* tasks, int64_t ti, int64_t tj) {
+  GemmGrid gg;
+  gg.ti = ti;
+  gg.tj = tj;
+  gg.cm = tasks[0].m;
+  gg.cn = tasks[0].n;
+  gg.M = (ti - 1) * gg.cm + tasks[(ti - 1) * tj].m;
+  gg.N = (tj - 1) * gg.cn + tasks[tj - 1].n;
+  return gg;
+}
+
 }  // namespace
 
 // Which kernel serves a chain set (host tables): the MFMA fast paths need
@@ -957,31 +868,20 @@ bool aligned16(int64_t x) { return (x & 15) == 0; }
 extern "C" int cubed_gemm_chain_path(const cubed_gemm_chain_t* tasks, int64_t ntasks,
                                      const cubed_gemm_seg_t* segs, int32_t in_dtype,
                                      int32_t out_dtype) {
-  if (in_dtype == CUBED_BF16 && (out_dtype == CUBED_F32 || out_dtype == CUBED_BF16)) {
-    for (int64_t t = 0; t < ntasks; ++t) {
-      const cubed_gemm_chain_t& T = tasks[t];
-      if (T.n < 8 || T.n % 8 || T.m < 1) return CUBED_GEMM_ANY;
-      for (int64_t i = T.seg0; i < T.seg0 + T.nseg; ++i) {
-        const cubed_gemm_seg_t& s = segs[i];
-        if (s.k < 32 || s.k % 8 || s.lda % 8 || s.ldb % 8 || !aligned16(s.a) || !aligned16(s.b))
-          return CUBED_GEMM_ANY;
-      }
+  const bool bf = in_dtype == CUBED_BF16 && (out_dtype == CUBED_F32 || out_dtype == CUBED_BF16);
+  if (!bf && !(in_dtype == CUBED_F32 && out_dtype == CUBED_F32)) return CUBED_GEMM_ANY;
+  const int64_t q = bf ? 8 : 4;  // elements per 16 bytes
+  for (int64_t t = 0; t < ntasks; ++t) {
+    const cubed_gemm_chain_t& T = tasks[t];
+    // (the n >= 8 floor is bf16's alone)
+    if ((bf && T.n < 8) || T.n % q || T.m < 1) return CUBED_GEMM_ANY;
+    for (int64_t i = T.seg0; i < T.seg0 + T.nseg; ++i) {
+      const cubed_gemm_seg_t& s = segs[i];
+      if (s.k < 32 || s.k % q || s.lda % q || s.ldb % q || !aligned16(s.a) || !aligned16(s.b))
+        return CUBED_GEMM_ANY;
     }
-    return CUBED_GEMM_MFMA;
   }
-  if (in_dtype == CUBED_F32 && out_dtype == CUBED_F32) {
-    for (int64_t t = 0; t < ntasks; ++t) {
-      const cubed_gemm_chain_t& T = tasks[t];
-      if (T.n % 4 || T.m < 1) return CUBED_GEMM_ANY;
-      for (int64_t i = T.seg0; i < T.seg0 + T.nseg; ++i) {
-        const cubed_gemm_seg_t& s = segs[i];
-        if (s.k < 32 || s.k % 4 || s.lda % 4 || s.ldb % 4 || !aligned16(s.a) || !aligned16(s.b))
-          return CUBED_GEMM_ANY;
-      }
-    }
-    return CUBED_GEMM_MFMA;
-  }
-  return CUBED_GEMM_ANY;
+  return CUBED_GEMM_MFMA;
 }
 
 extern "C" int cubed_gemm_chain(const cubed_gemm_chain_t* tasks, const cubed_gemm_chain_t* d_tasks,
@@ -1019,27 +919,21 @@ extern "C" int cubed_gemm_chain(const cubed_gemm_chain_t* tasks, const cubed_gem
     // (gemm_bf16_w4l.h: 1256-1258 TF on config 5) whenever every segment
     // spans a 64-k A tile; otherwise the round-2 ping-pong schedule
     // (1072-1098 TF, profiles/r02_gemm_bf16_variants.log)
-    bool w4l = true;
-    for (int64_t t = 0; t < ntasks && w4l; ++t)
-      for (int64_t i = tasks[t].seg0; i < tasks[t].seg0 + tasks[t].nseg; ++i)
-        if (segs[i].k < 64) { w4l = false; break; }
-    if (w4l) {
+    if (all_segments_k64(tasks, ntasks, segs)) {
       if (out_dtype == CUBED_BF16)
-        hipLaunchKernelGGL((k_gemm_bf16_w4l<true>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{},
-                           nullptr);
+        hipLaunchKernelGGL((k_gemm_bf16_w4l<true>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{});
       else
-        hipLaunchKernelGGL((k_gemm_bf16_w4l<false>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{},
-                           nullptr);
+        hipLaunchKernelGGL((k_gemm_bf16_w4l<false>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{});
     } else if (out_dtype == CUBED_BF16)
-      hipLaunchKernelGGL((k_gemm_bf16_chain<true, 0, 1>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{});
+      hipLaunchKernelGGL((k_gemm_bf16_chain<true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{});
     else
-      hipLaunchKernelGGL((k_gemm_bf16_chain<false, 0, 1>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{});
+      hipLaunchKernelGGL((k_gemm_bf16_chain<false>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, GemmGrid{});
   } else if (path == CUBED_GEMM_MFMA && in_dtype == CUBED_F32) {
     if (!d_zero) return fail("the f32 path needs a zero page");
     const int64_t tm = (max_m + HF_BM - 1) / HF_BM, tn = (max_n + HF_BN - 1) / HF_BN;
     const int64_t blocks = ntasks * tm * tn;
     if (blocks > 0x7fffffff) return fail("grid too large");
-    hipLaunchKernelGGL((k_gemm_f32_chain<16, 4>), dim3((unsigned)blocks), dim3(512), 0, st, d_tasks, d_segs, tm,
+    hipLaunchKernelGGL((k_gemm_f32_chain<false>), dim3((unsigned)blocks), dim3(512), 0, st, d_tasks, d_segs, tm,
                        tn, (const char*)d_zero, GemmGrid{});
   } else {
     const int64_t tm = (max_m + TM - 1) / TM, tn = (max_n + TN - 1) / TN;
@@ -1064,13 +958,11 @@ extern "C" int cubed_gemm_chain(const cubed_gemm_chain_t* tasks, const cubed_gem
         return CUBED_E_DTYPE;
     }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+  return launch_status();
 }
 
-// ---- grid tiling (f32 MFMA): the chain set is a ti x tj chunk grid of one
-// (M, N) output, task I*tj + J = chunk (I, J); see k_gemm_f32_chain<.., GRID>.
+// ---- grid tiling (f32 and bf16 MFMA): the chain set is a ti x tj chunk grid
+// of one (M, N) output, task I*tj + J = chunk (I, J); see GemmGrid.
 extern "C" int cubed_gemm_grid_check(const cubed_gemm_chain_t* tasks, int64_t ti, int64_t tj,
                                      const cubed_gemm_seg_t* segs, int64_t nsegs, int32_t in_dtype,
                                      int32_t out_dtype) {
@@ -1118,13 +1010,7 @@ extern "C" int cubed_gemm_chain_grid(const cubed_gemm_chain_t* tasks, const cube
                                      int32_t out_dtype, const void* d_zero, void* stream) {
   if (!d_tasks || !d_segs || !d_zero) return fail("grid: bad argument");
   if (int rc = cubed_gemm_grid_check(tasks, ti, tj, segs, nsegs, in_dtype, out_dtype)) return rc;
-  GemmGrid gg;
-  gg.ti = ti;
-  gg.tj = tj;
-  gg.cm = tasks[0].m;
-  gg.cn = tasks[0].n;
-  gg.M = (ti - 1) * gg.cm + tasks[(ti - 1) * tj].m;
-  gg.N = (tj - 1) * gg.cn + tasks[tj - 1].n;
+  const GemmGrid gg = grid_of(tasks, ti, tj);
   const int64_t tm = (gg.M + HF_BM - 1) / HF_BM, tn = (gg.N + HF_BN - 1) / HF_BN;
   if (tm * tn > 0x7fffffff) return fail("grid too large");
   const dim3 grid((unsigned)(tm * tn)), blk(512);
@@ -1133,32 +1019,30 @@ extern "C" int cubed_gemm_chain_grid(const cubed_gemm_chain_t* tasks, const cube
   static_assert(HB_BM == HF_BM && HB_BN == HF_BN, "one tile size");
   // bf16: the one-wave full-line kernel (gemm_bf16_w4l.h) when every segment
   // spans a 64-k A tile, else the ping-pong kernel's grid form
-  bool w4l = in_dtype == CUBED_BF16;
-  for (int64_t i = 0; i < ti * tj && w4l; ++i)
-    for (int64_t s = tasks[i].seg0; s < tasks[i].seg0 + tasks[i].nseg; ++s)
-      if (segs[s].k < 64) { w4l = false; break; }
-  if (w4l && out_dtype == CUBED_BF16)
-    hipLaunchKernelGGL((k_gemm_bf16_w4l<true, 4, false, 0, true>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z,
-                       gg, nullptr);
+  const bool bf = in_dtype == CUBED_BF16, obf = out_dtype == CUBED_BF16;
+  const bool w4l = bf && all_segments_k64(tasks, ti * tj, segs);
+  if (w4l && obf)
+    hipLaunchKernelGGL((k_gemm_bf16_w4l<true, true>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z, gg);
   else if (w4l)
-    hipLaunchKernelGGL((k_gemm_bf16_w4l<false, 4, false, 0, true>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z,
-                       gg, nullptr);
-  else if (in_dtype == CUBED_BF16 && out_dtype == CUBED_BF16)
-    hipLaunchKernelGGL((k_gemm_bf16_chain<true, 0, 1, HB_NS, 4, true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, gg);
-  else if (in_dtype == CUBED_BF16)
-    hipLaunchKernelGGL((k_gemm_bf16_chain<false, 0, 1, HB_NS, 4, true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, gg);
+    hipLaunchKernelGGL((k_gemm_bf16_w4l<false, true>), grid, dim3(256), 0, st, d_tasks, d_segs, tm, tn, z, gg);
+  else if (bf && obf)
+    hipLaunchKernelGGL((k_gemm_bf16_chain<true, true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, gg);
+  else if (bf)
+    hipLaunchKernelGGL((k_gemm_bf16_chain<false, true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, gg);
   else
-    hipLaunchKernelGGL((k_gemm_f32_chain<16, 4, false, true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, gg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+    hipLaunchKernelGGL((k_gemm_f32_chain<true>), grid, blk, 0, st, d_tasks, d_segs, tm, tn, z, gg);
+  return launch_status();
 }
 
-// ---- packed operands (bf16: gemm_bf16_w4p.h, f32: gemm_f32_w4p.h): the chain set must be a
-// regular chunk grid (cubed_gemm_grid_check) of ONE product -- segment s of
-// every task in chunk row I reads the same A chunk, of every task in chunk
-// column J the same B chunk.
+// ---- packed operands (gemm_bf16_pack.h; GEMMs gemm_bf16_8p.h, gemm_f32_w4p.h):
+// the chain set must be a regular chunk grid (cubed_gemm_grid_check) of ONE
+// product -- segment s of every task in chunk row I reads the same A chunk, of
+// every task in chunk column J the same B chunk.
 namespace {
+// one k block of a packed panel: bf16 64-deep tiles of 32 KiB, f32 16-deep steps of 16 KiB
+int64_t kblock_k(int32_t in_dtype) { return in_dtype == CUBED_BF16 ? 64 : WPF_BK; }
+int64_t kblock_bytes(int32_t in_dtype) { return in_dtype == CUBED_BF16 ? WL_ATILE : WPF_SA; }
+
 constexpr int64_t PACK_SKEW = 0;  // bytes added to every panel's span (L2 set spread)
 int pack_plan(const cubed_gemm_chain_t* tasks, int64_t ti, int64_t tj, const cubed_gemm_seg_t* segs, int64_t nsegs,
               int32_t in_dtype, int32_t out_dtype, PackPlan& pp, GemmGrid& gg) {
@@ -1178,12 +1062,7 @@ int pack_plan(const cubed_gemm_chain_t* tasks, int64_t ti, int64_t tj, const cub
           return CUBED_E_LAYOUT;
         }
       }
-  gg.ti = ti;
-  gg.tj = tj;
-  gg.cm = tasks[0].m;
-  gg.cn = tasks[0].n;
-  gg.M = (ti - 1) * gg.cm + tasks[(ti - 1) * tj].m;
-  gg.N = (tj - 1) * gg.cn + tasks[tj - 1].n;
+  gg = grid_of(tasks, ti, tj);
   pp.ti = ti;
   pp.tj = tj;
   pp.cm = gg.cm;
@@ -1193,19 +1072,16 @@ int pack_plan(const cubed_gemm_chain_t* tasks, int64_t ti, int64_t tj, const cub
   pp.K = tasks[0].ktot;
   pp.TM = (pp.M + HB_BM - 1) / HB_BM;
   pp.TN = (pp.N + HB_BN - 1) / HB_BN;
-  // k blocks: bf16 64-deep tiles (32 KiB per panel), f32 16-deep steps (16 KiB)
-  pp.KTL = in_dtype == CUBED_BF16 ? (pp.K + 63) / 64 : (pp.K + WPF_BK - 1) / WPF_BK;
+  const int64_t kb = kblock_k(in_dtype);
+  pp.KTL = (pp.K + kb - 1) / kb;
   if (pp.TM * pp.TN > 0x7fffffff) return fail("grid too large");
-  pp.pstride = pp.KTL * (in_dtype == CUBED_BF16 ? WL_ATILE : WPF_SA) + PACK_SKEW;
+  pp.pstride = pp.KTL * kblock_bytes(in_dtype) + PACK_SKEW;
   pp.apstride = pp.pstride;
-  pp.akstride = in_dtype == CUBED_BF16 ? WL_ATILE : WPF_SA;
+  pp.akstride = kblock_bytes(in_dtype);
   pp.kt0 = 0;
   pp.kt1 = pp.KTL;
   return 0;
 }
-
-int64_t kblock_k(int32_t in_dtype) { return in_dtype == CUBED_BF16 ? 64 : WPF_BK; }
-int64_t kblock_bytes(int32_t in_dtype) { return in_dtype == CUBED_BF16 ? WL_ATILE : WPF_SA; }
 
 // the multi-GPU A image: k-major blocks of the whole A (K blocks x TM panels)
 void dist_image(PackPlan& pp, int32_t in_dtype) {
@@ -1298,9 +1174,7 @@ extern "C" int cubed_gemm_dist_pack_a(const cubed_gemm_chain_t* a_tasks, const c
     hipLaunchKernelGGL(k_pack_a_f32, ga, dim3(256), 0, st, d_a_tasks, d_a_segs, pp, (char*)d_image);
   else
     hipLaunchKernelGGL(k_pack_a, ga, dim3(256), 0, st, d_a_tasks, d_a_segs, pp, (char*)d_image);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+  return launch_status();
 }
 
 // the rank's local product: its C chunks (ti x tj grid, columns it owns), B
@@ -1341,9 +1215,7 @@ extern "C" int cubed_gemm_dist_pack_b(const cubed_gemm_chain_t* tasks, const cub
     hipLaunchKernelGGL(k_pack_b_f32, gb, dim3(256), 0, st, d_tasks, d_segs, pp, (char*)d_ws);
   else
     hipLaunchKernelGGL(k_pack_bt, gb, dim3(256), 0, st, d_tasks, d_segs, pp, (char*)d_ws);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+  return launch_status();
 }
 
 extern "C" int cubed_gemm_dist_gemm(const cubed_gemm_chain_t* tasks, const cubed_gemm_chain_t* d_tasks, int64_t ti,
@@ -1363,15 +1235,15 @@ extern "C" int cubed_gemm_dist_gemm(const cubed_gemm_chain_t* tasks, const cubed
   const dim3 grid((unsigned)(pp.TM * pp.TN));
   const char* PA = (const char*)d_image;
   const char* PB = (const char*)d_ws;
+  // (no round alignment here: the ranks' launches carry no counters)
+  unsigned* const no_counters = nullptr;
   if (in_dtype == CUBED_F32)
-    hipLaunchKernelGGL((k_gemm_f32_w4p<false>), grid, dim3(256), 0, st, d_tasks, PA, PB, pp, gg, nullptr);
+    hipLaunchKernelGGL(k_gemm_f32_w4p, grid, dim3(256), 0, st, d_tasks, PA, PB, pp, gg);
   else if (out_dtype == CUBED_BF16)
-    hipLaunchKernelGGL((k_gemm_bf16_8p<true>), grid, dim3(512), 0, st, d_tasks, PA, PB, pp, gg, nullptr);
+    hipLaunchKernelGGL((k_gemm_bf16_8p<true>), grid, dim3(512), 0, st, d_tasks, PA, PB, pp, gg, no_counters);
   else
-    hipLaunchKernelGGL((k_gemm_bf16_8p<false>), grid, dim3(512), 0, st, d_tasks, PA, PB, pp, gg, nullptr);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+    hipLaunchKernelGGL((k_gemm_bf16_8p<false>), grid, dim3(512), 0, st, d_tasks, PA, PB, pp, gg, no_counters);
+  return launch_status();
 }
 
 extern "C" int64_t cubed_gemm_pack_bytes(const cubed_gemm_chain_t* tasks, int64_t ti, int64_t tj,
@@ -1407,25 +1279,22 @@ extern "C" int cubed_gemm_chain_packed(const cubed_gemm_chain_t* tasks, const cu
   if (in_dtype == CUBED_F32) {
     hipLaunchKernelGGL(k_pack_a_f32, ga, dim3(256), 0, st, d_tasks, d_segs, pp, PA);
     hipLaunchKernelGGL(k_pack_b_f32, gb, dim3(256), 0, st, d_tasks, d_segs, pp, PB);
-    hipLaunchKernelGGL((k_gemm_f32_w4p<false>), grid, dim3(256), 0, st, d_tasks, (const char*)PA, (const char*)PB, pp,
-                       gg, nullptr);
+    hipLaunchKernelGGL(k_gemm_f32_w4p, grid, dim3(256), 0, st, d_tasks, (const char*)PA, (const char*)PB, pp, gg);
   } else {
     hipLaunchKernelGGL(k_pack_a, ga, dim3(256), 0, st, d_tasks, d_segs, pp, PA);
     hipLaunchKernelGGL(k_pack_bt, gb, dim3(256), 0, st, d_tasks, d_segs, pp, PB);
     // two waves per SIMD on the packed image (gemm_bf16_8p.h; round 6:
     // 1410-1424 TF against the one-wave w4p kernel's 1301-1317, bit-identical),
-    // each XCD's rounds of tiles aligned on counters zeroed here (E8_ROUNDS)
-    unsigned long long* ctr = (unsigned long long*)(PB + bytesB);
+    // each XCD's rounds of tiles aligned on counters zeroed here (ROUNDS)
+    unsigned* ctr = (unsigned*)(PB + bytesB);
     hipError_t me = hipMemsetAsync(ctr, 0, PACK_CTR_BYTES, st);
     if (me != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(me)); return (int)me; }
     if (out_dtype == CUBED_BF16)
-      hipLaunchKernelGGL((k_gemm_bf16_8p<true, false, E8_ROUNDS>), grid, dim3(512), 0, st, d_tasks, (const char*)PA,
+      hipLaunchKernelGGL((k_gemm_bf16_8p<true, true>), grid, dim3(512), 0, st, d_tasks, (const char*)PA,
                          (const char*)PB, pp, gg, ctr);
     else
-      hipLaunchKernelGGL((k_gemm_bf16_8p<false, false, E8_ROUNDS>), grid, dim3(512), 0, st, d_tasks, (const char*)PA,
+      hipLaunchKernelGGL((k_gemm_bf16_8p<false, true>), grid, dim3(512), 0, st, d_tasks, (const char*)PA,
                          (const char*)PB, pp, gg, ctr);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+  return launch_status();
 }

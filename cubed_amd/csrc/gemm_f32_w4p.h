@@ -1,13 +1,14 @@
 // gemm_f32_w4p.h -- the library's f32 chained GEMM on PACKED operands
-// (round 5; included by gemm_chain.hip after gemm_bf16_w4p.h, launched by
-// cubed_gemm_chain_packed for f32 inputs).
+// (round 5; included by gemm_chain.hip after gemm_bf16_pack.h, which holds
+// PackPlan and seg_at; launched by cubed_gemm_chain_packed and
+// cubed_gemm_dist_gemm for f32 inputs).
 //
-// tools/gemm_f32_w4.h put one wave per SIMD on k_gemm_f32_chain's LDS image
-// and measured parity, not more: its main loop ran 70.5-72.7 cycles per
-// v_mfma_f32_32x32x2_f32 against 65.5 for the same instruction stream without
-// the per-step bookkeeping (segment walk, per-lane piece addresses;
-// profiles/r05_mfma_flow.log k_flow32, profiles/r05_gemm_f32_w4.log).  Packing
-// removes that bookkeeping as it does for bf16 (gemm_bf16_w4p.h): A is
+// One wave per SIMD on k_gemm_f32_chain's LDS image (the retired
+// tools/gemm_f32_w4.h) measured parity, not more: its main loop ran 70.5-72.7
+// cycles per v_mfma_f32_32x32x2_f32 against 65.5 for the same instruction
+// stream without the per-step bookkeeping (segment walk, per-lane piece
+// addresses; profiles/r05_mfma_flow.log k_flow32, profiles/r05_gemm_f32_w4.log).
+// Packing removes that bookkeeping as it does for bf16 (gemm_bf16_pack.h): A is
 // rewritten per 256-row panel and 16-deep k step into the 16 KiB A half of the
 // LDS stage (row r at r * 64, 16-B slot s holding k chunk s ^ ((r >> 2) & 3)),
 // B per 256-column panel and step into the 16 KiB B half (k-row major, 1 KiB
@@ -15,8 +16,8 @@
 // zero.  A wave's 8 pieces per step are then 1 KiB runs at fixed offsets from
 // two uniform bases that advance 16 KiB per step.
 //
-// Same schedule and fragment permutations as tools/gemm_f32_w4.h (itself
-// k_gemm_f32_chain's): per output element the same f32 chain over K --
+// Same fragment permutations as k_gemm_f32_chain: per output element the same
+// f32 chain over K --
 // bit-identical to cubed_gemm_chain / cubed_gemm_chain_grid.
 #pragma once
 
@@ -93,27 +94,22 @@ __global__ __launch_bounds__(256) void k_pack_b_f32(const cubed_gemm_chain_t* __
 // p % 4 with fragments read during step p - 1, reads step p + 1's fragments
 // and stages step p + 4 into stage p % 4 (free once every wave passed step p's
 // barrier).  The wait before step p's barrier leaves steps p + 2 and p + 3's
-// 16 pieces in flight.  STAMP: per-wave main-loop cycles (probe builds only).
-// LOCK: tile order xcd_lockstep (probe: false = xcd_remap's contiguous ranges).
-// SYNC (probe): round_wait / round_done around the K loop, counters at stamp_out.
-template <bool STAMP = false, bool LOCK = true, bool SYNC = false>
+// 16 pieces in flight.
+// Tile order xcd_lockstep, as the bf16 kernel's (equal to xcd_remap's
+// contiguous ranges for f32: 885.6 against 886.9 ms,
+// profiles/r06_gemm_tile_order.log).  Measured and dropped: the bf16 kernel's
+// round alignment (round_wait), 882.9-883.8 against 878.5-879.5 ms
+// (profiles/r06_gemm_round_sync.log).
 __global__ __launch_bounds__(256, 1) void k_gemm_f32_w4p(const cubed_gemm_chain_t* __restrict__ tasks,
                                                       const char* __restrict__ PA, const char* __restrict__ PB,
-                                                      PackPlan pp, GemmGrid gg,
-                                                      unsigned long long* __restrict__ stamp_out) {
+                                                      PackPlan pp, GemmGrid gg) {
   constexpr int G = 2, LPS = 8;
   __shared__ __attribute__((aligned(1024))) char lds_[WPF_NS * WPF_STAGE];
   CUBED_L char* lds = (CUBED_L char*)lds_;
   int64_t t, m0, n0;
-  const int64_t lt = LOCK ? xcd_lockstep(blockIdx.x, gridDim.x, 4 * pp.TN, pp.TM / 4) : xcd_remap(blockIdx.x, gridDim.x);
-  tile_of<HF_BM, HF_BN, 4>(lt, pp.TM, pp.TN, t, m0, n0);
+  tile_of<HF_BM, HF_BN, 4>(xcd_lockstep(blockIdx.x, gridDim.x, 4 * pp.TN, pp.TM / 4), pp.TM, pp.TN, t, m0, n0);
   const int64_t M = pp.M, N = pp.N;
-  unsigned* const rctr = SYNC ? (unsigned*)stamp_out : nullptr;
-  if (t != 0 || m0 >= M || n0 >= N) {
-    if constexpr (SYNC) round_done(rctr, blockIdx.x);
-    return;
-  }
-  if constexpr (SYNC) round_wait(rctr, blockIdx.x, 32);
+  if (t != 0 || m0 >= M || n0 >= N) return;
   const int64_t nst = pp.KTL;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -233,18 +229,9 @@ __global__ __launch_bounds__(256, 1) void k_gemm_f32_w4p(const cubed_gemm_chain_
   using Full = std::integral_constant<bool, true>;
   using Tail = std::integral_constant<bool, false>;
   int64_t p = 0;
-  unsigned long long t0 = 0, t1 = 0;
-  if constexpr (STAMP) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
   for (; p + 1 + WPF_NS < nst; p += 2) {
     step(p, f0, f1, Full{});
     step(p + 1, f1, f0, Full{});
-  }
-  if constexpr (STAMP) {
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
-    if (lane == 0) {
-      stamp_out[(blockIdx.x * 4 + w) * 2] = t1 - t0;
-      stamp_out[(blockIdx.x * 4 + w) * 2 + 1] = (unsigned long long)p;
-    }
   }
   // tail (at most 5 steps, staging the last ones): step p's fragments are in f0
   for (; p < nst; ++p) {
@@ -252,7 +239,6 @@ __global__ __launch_bounds__(256, 1) void k_gemm_f32_w4p(const cubed_gemm_chain_
     f0 = f1;
   }
 #undef WPF_PIECE
-  if constexpr (SYNC) round_done(rctr, blockIdx.x);
 
   // epilogue: accumulator (rb, q) register r = row wm + 32 rb + (r&3) +
   // 8 (r>>2) + 4h, column wn + 4 r32 + q: one float4 per (rb, r)

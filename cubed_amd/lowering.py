@@ -965,7 +965,7 @@ class GemmLaunch:
     # one-wave full-line kernel runs 1251-1256 TF per chunk vs 1076-1080 grid
     # (its grid form keeps per-lane chunk selects live through the K loop;
     # profiles/r05_gemm_bf16_ab.log, ping-pong grid 1048-1050)
-    GRID_INPUTS = {ir.dtype_code(np.float32)}  # (tools/gemm_ab.sh widens it for A/B runs)
+    GRID_INPUTS = {ir.dtype_code(np.float32)}  # (tests and A/B runs widen it to reach the bf16 grid kernels)
     # bf16 / f32 chunk grids of one product take the packed-operand kernels
     # (cubed_gemm_chain_packed): both operands rewritten once into the GEMM's
     # LDS image, then whole-matrix tiles -- config 5 bf16 GEMM 1316 TF vs 1214

@@ -607,7 +607,7 @@ class DistPiecesLaunch:
 
 
 # k block of the packed GEMM images (bf16: 64-deep tiles of 32 KiB per
-# 256-row panel; f32: 16-deep steps of 16 KiB), csrc/gemm_bf16_w4p.h / _f32_
+# 256-row panel; f32: 16-deep steps of 16 KiB), csrc/gemm_bf16_pack.h / gemm_f32_
 KBLOCK = {2: (64, 32768), 4: (16, 16384)}
 LINK_GBPS = 153.0  # ASSUMED xGMI rate per link and direction (MI355X_MICROARCH.md); rehearsal predictions only
 

@@ -217,7 +217,10 @@ def test_bf16_astype_round_trip(ex):
 
 
 @pytest.mark.parametrize("shapes", [((600, 1200), (1200, 704), (300, 400), (400, 352)),    # 2 x 2 regular grid
-                                    ((700, 1304), (1304, 1000), (300, 400), (400, 352))])  # ragged last row / column
+                                    ((700, 1304), (1304, 1000), (300, 400), (400, 352)),   # ragged last row / column
+                                    # five 40-deep segments (< 64 k: bf16 takes the ping-pong kernel's grid
+                                    # form), the smallest chunks the grid check passes
+                                    ((520, 200), (200, 520), (260, 40), (40, 264))])
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_grid_tiling_bit_identical(gpu_executor, shapes, dt, monkeypatch):
     """f32 chains over a regular chunk grid run as ONE grid-tiled launch
