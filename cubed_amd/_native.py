@@ -37,7 +37,7 @@ MAX_EPI = 16
 MAX_CONSTS = 16
 NREGS = 6
 
-ABI_VERSION = 18  # include/cubed_amd.h CUBED_ABI_VERSION
+ABI_VERSION = 19  # include/cubed_amd.h CUBED_ABI_VERSION
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcubed_amd.so")
 
 
@@ -107,6 +107,26 @@ SCAN_TASK_DTYPE = np.dtype([
 ])
 SCAN_ROWS, SCAN_COLS, SCAN_COLS_V4 = 0, 1, 2
 
+# cubed_sort_task_t (one chunk of a sort, seen as (rows, n)) and
+# cubed_merge_task_t (one output chunk of a merge-split of two sorted chunks)
+SORT_TASK_DTYPE = np.dtype([
+    ("src_base", np.int64), ("dst_base", np.int64), ("dst_idx_base", np.int64),
+    ("scratch_base", np.int64), ("scratch_idx_base", np.int64),
+    ("rows", np.int64), ("n", np.int64),
+    ("src_row_stride", np.int64), ("dst_row_stride", np.int64),
+    ("index_base", np.int64),
+])
+MERGE_TASK_DTYPE = np.dtype([
+    ("lo_base", np.int64), ("lo_idx_base", np.int64),
+    ("hi_base", np.int64), ("hi_idx_base", np.int64),
+    ("dst_base", np.int64), ("dst_idx_base", np.int64),
+    ("rows", np.int64), ("na", np.int64), ("nb", np.int64),
+    ("lo_row_stride", np.int64), ("hi_row_stride", np.int64), ("dst_row_stride", np.int64),
+    ("role", np.int64),
+])
+SORT_DESCENDING, SORT_PAIRS = 1, 2
+MERGE_LOW, MERGE_HIGH, MERGE_COPY = 0, 1, 2
+
 
 class NativeError(RuntimeError):
     pass
@@ -143,6 +163,14 @@ def lib():
     L.cubed_scan_path.restype = c_int
     L.cubed_scan_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
     L.cubed_scan_chunks.restype = c_int
+    L.cubed_sort_tile.argtypes = []
+    L.cubed_sort_tile.restype = c_int64
+    L.cubed_sort_plan.argtypes = [c_void_p, c_int64, c_int32, c_int32, POINTER(c_int32), POINTER(c_int64)]
+    L.cubed_sort_plan.restype = c_int
+    L.cubed_sort_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_sort_chunks.restype = c_int
+    L.cubed_merge_split.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_merge_split.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -244,6 +272,7 @@ EXPORTED_SYMBOLS = (
     "cubed_gemm_grid_check", "cubed_gemm_chain_grid", "cubed_gemm_pack_bytes", "cubed_gemm_chain_packed",
     "cubed_gemm_dist_image_bytes", "cubed_gemm_dist_pack_a", "cubed_gemm_dist_b_bytes", "cubed_gemm_dist_pack_b",
     "cubed_gemm_dist_gemm", "cubed_scan_path", "cubed_scan_chunks",
+    "cubed_sort_tile", "cubed_sort_plan", "cubed_sort_chunks", "cubed_merge_split",
 )
 
 
@@ -254,6 +283,21 @@ def scan_path(rows: np.ndarray, vtype: int) -> int:
     if path < 0:
         check(path, "cubed_scan_path")
     return path
+
+
+def sort_tile() -> int:
+    """Elements one workgroup of the tile sort orders in LDS (host only)."""
+    return int(lib().cubed_sort_tile())
+
+
+def sort_plan(rows: np.ndarray, ktype: int, pairs: bool):
+    """(merge passes, scratch bytes) of a host table of SORT_TASK_DTYPE rows
+    (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=SORT_TASK_DTYPE)
+    passes, nbytes = ctypes.c_int32(0), ctypes.c_int64(0)
+    check(lib().cubed_sort_plan(rows.ctypes.data, len(rows), ktype, int(bool(pairs)),
+                                ctypes.byref(passes), ctypes.byref(nbytes)), "cubed_sort_plan")
+    return passes.value, nbytes.value
 
 
 INCLUDE_DIRS = ";".join([os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"),

@@ -817,6 +817,101 @@ def scan(x: "Array", axis: int) -> "Array":
                              fusable=False)
 
 
+# ------------------------------------------------------------------ sorts
+
+
+def sort_network(nb: int):
+    """Rounds of (lower, upper) block pairs that sort ``nb`` sorted blocks by
+    merge-splits: the normalised bitonic network over ``P = next_pow2(nb)``
+    positions.  For k = 2, 4, .., P one flip round (block b with b ^ (k - 1)),
+    then rounds j = k/4, .., 1 (b with b ^ j).  In a pair the lower block keeps
+    the first ``len(lower)`` elements of the merge and the upper one the rest,
+    so a ragged last block keeps its length.  Positions at or above ``nb``
+    stand for empty blocks after every real one: their pairs are left out (the
+    partner is copied), and so is a round without a real pair."""
+    if nb < 1:
+        raise ValueError("sort_network needs at least one block")
+    P = 1
+    while P < nb:
+        P *= 2
+    rounds = []
+
+    def add(partner):
+        pairs = [(b, partner(b)) for b in range(nb) if b < partner(b) < nb]
+        if pairs:
+            rounds.append(pairs)
+
+    k = 2
+    while k <= P:
+        add(lambda b: b ^ (k - 1))
+        j = k // 4
+        while j >= 1:
+            add(lambda b: b ^ j)
+            j //= 2
+        k *= 2
+    return rounds
+
+
+class _merge_block_function:
+    """Output block ``b`` of one round of the block network reads its own
+    chunk of the previous round and its partner's, the lower block of the pair
+    first; a block without a partner reads only its own."""
+
+    def __init__(self, name, axis, pairs):
+        self.name, self.axis = name, axis
+        self.partner = {}
+        for lo, hi in pairs:
+            self.partner[lo], self.partner[hi] = hi, lo
+
+    def __call__(self, out_key):
+        coords = tuple(out_key[1:])
+        b = coords[self.axis]
+        p = self.partner.get(b)
+        if p is None:
+            return [(self.name,) + coords]
+        other = coords[:self.axis] + (p,) + coords[self.axis + 1:]
+        lo, hi = (coords, other) if b < p else (other, coords)
+        return [(self.name,) + lo, (self.name,) + hi]
+
+
+def sort(x: "Array", axis: int, descending: bool = False, pairs: bool = False) -> "Array":
+    """``x`` sorted along ``axis`` (``pairs=False``, same dtype) or the int64
+    indices that sort it (``pairs=True``), same shape and chunks.  ``x.dtype``
+    is one of the sort key types (float32, float64, 32- and 64-bit integers).
+    Stable: ties go to the smaller index along the axis in both directions.
+
+    The kernels sort rows, so an axis with a longer dim after it is moved
+    last by ``permute_dims`` and moved back afterwards (two extra passes; the
+    first one materialises, a sort is never fused).  One block along the axis:
+    one ``"chunk"`` op.  ``nb`` blocks: the chunk op, then one ``"merge"`` op
+    of ``nb`` tasks per round of ``sort_network(nb)``.  No task reads more
+    than two chunks; every op passes the ordinary projected-memory check."""
+    from ..array_api.manipulation_functions import permute_dims
+    from ..chunkfuncs import _arg_aggregate
+
+    nd = x.ndim
+    if builtins.any(s > 1 for s in x.shape[axis + 1:]):
+        order = [d for d in range(nd) if d != axis] + [axis]
+        y = sort(permute_dims(x, tuple(order)), nd - 1, descending, pairs)
+        return permute_dims(y, tuple(int(i) for i in np.argsort(order)))
+    dtype = np.dtype(x.dtype)
+    work_dtype = ir.sort_pairs_dtype(dtype) if pairs else dtype
+    inds = tuple(range(nd))
+    # the merge passes inside a chunk ping-pong with a scratch copy of it
+    chunk_mem = chunk_memory(work_dtype, x.chunksize)
+    cur = blockwise(ir.SortProgram(axis=axis, descending=descending, pairs=pairs, dtype=dtype),
+                    inds, x, inds, dtype=work_dtype, extra_projected_mem=chunk_mem, fusable=False)
+    for rnd in sort_network(x.numblocks[axis]):
+        # the partner's chunk is a second chunk of the one array argument
+        cur = general_blockwise(
+            ir.SortProgram(axis=axis, descending=descending, pairs=pairs, dtype=dtype, kind="merge", nargs=2),
+            _merge_block_function(cur.name, axis, rnd), cur, shape=cur.shape, dtype=work_dtype,
+            chunks=cur.chunks, extra_projected_mem=2 * chunk_mem, fusable=False)
+    if pairs:
+        cur = blockwise(_arg_aggregate.program(nd, work_dtype), inds, cur, inds, dtype=np.int64)
+    return cur
+
+
 def _normalize_split_every(split_every, axis):
     split_every = split_every or 4
     if isinstance(split_every, dict):

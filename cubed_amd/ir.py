@@ -436,6 +436,33 @@ class ScanProgram(Program):
     name: str = "scan"
 
 
+@dataclass(frozen=True, eq=False)
+class SortProgram(Program):
+    """Per task, along ``axis`` (the last dim, or every later dim has extent
+    1).  ``kind="chunk"``: the sorted chunk of argument 0.  ``kind="merge"``:
+    the task's share of the merge of two sorted chunks -- its own block and its
+    partner of this round of the block network (``core.ops.sort_network``): the
+    lower block of a pair keeps the first elements of the merge, the upper one
+    the rest; the block function names the lower chunk first and gives a block
+    without a partner only its own chunk, which is copied.  ``dtype`` is the
+    key type (float32, float64, a 32- or 64-bit integer).  ``pairs``: the
+    elements are {v: key, i: int64 index along the axis}, ordered by (key,
+    index); a chunk op reads plain keys and makes the indices.  Not an
+    expression program: never fused, and the rewrites leave it alone."""
+    axis: int = 0
+    descending: bool = False
+    pairs: bool = False
+    dtype: np.dtype = np.dtype("float64")
+    kind: str = "chunk"
+    nargs: int = 1
+    name: str = "sort"
+
+
+def sort_pairs_dtype(dtype) -> np.dtype:
+    """Element type of the arrays a pairs-mode sort works on."""
+    return np.dtype([("v", np.dtype(dtype)), ("i", np.int64)])
+
+
 def scan_acc_dtype(dtype) -> np.dtype:
     """Accumulator (and carry) type of a scan over values of ``dtype``."""
     dtype = np.dtype(dtype)

@@ -391,6 +391,138 @@ class ScanLaunch:
                   "cubed_scan_chunks")
 
 
+# ------------------------------------------------------------------ sorts
+
+
+def sort_ktype(dtype) -> int:
+    dtype = np.dtype(dtype)
+    if dtype in [np.dtype(t) for t in (np.float32, np.float64, np.int32, np.int64, np.uint32, np.uint64)]:
+        return ir.dtype_code(dtype)
+    raise LoweringError(f"sort of {dtype} keys is not lowered (float32, float64, 32- and 64-bit integers)")
+
+
+def _rows_n(view: ArrView, axis: int, what: str):
+    """A compact C-ordered chunk view as (rows, n): ``axis`` is its last dim
+    with more than one element."""
+    ext = list(view.extent)
+    if list(view.stride) != list(c_strides(ext)):
+        raise LoweringError(f"{what} chunks must be compact and C-ordered")
+    if math.prod(ext[axis + 1:]) != 1:
+        raise LoweringError(f"{what} runs along the last axis of a chunk, not axis {axis} of extent {ext}")
+    return math.prod(ext[:axis]), ext[axis]
+
+
+def sort_task(src: ArrView, dst: ArrView, axis: int, index_base: int = 0, dst_idx: Optional[ArrView] = None):
+    """One nat.SORT_TASK_DTYPE row: the chunk view ``src`` sorted along
+    ``axis`` into ``dst`` (and, pairs, the int64 indices ``index_base + i``
+    into ``dst_idx``).  The scratch addresses are filled in by SortLaunch."""
+    rows, n = _rows_n(src, axis, "sort")
+    for v in (dst, dst_idx):
+        if v is not None and _rows_n(v, axis, "sort") != (rows, n):
+            raise LoweringError(f"sort chunk extents differ: {list(src.extent)} -> {list(v.extent)}")
+    row = np.zeros((), dtype=nat.SORT_TASK_DTYPE)
+    row["src_base"], row["dst_base"] = src.base, dst.base
+    row["dst_idx_base"] = dst_idx.base if dst_idx is not None else 0
+    row["rows"], row["n"] = rows, n
+    row["src_row_stride"] = row["dst_row_stride"] = n
+    row["index_base"] = index_base
+    return row
+
+
+def merge_task(lo, hi, dst, axis: int, role: int):
+    """One nat.MERGE_TASK_DTYPE row.  ``lo``, ``hi``, ``dst``: (key view, index
+    view or None) of the lower chunk, the upper chunk (None for MERGE_COPY)
+    and the output chunk, which has the extent of the lower (MERGE_LOW,
+    MERGE_COPY) or the upper chunk (MERGE_HIGH)."""
+    rows, na = _rows_n(lo[0], axis, "merge")
+    nb = 0
+    if role != nat.MERGE_COPY:
+        rows_b, nb = _rows_n(hi[0], axis, "merge")
+        if rows_b != rows:
+            raise LoweringError(f"merge chunks of {rows} and {rows_b} rows")
+    if _rows_n(dst[0], axis, "merge") != (rows, nb if role == nat.MERGE_HIGH else na):
+        raise LoweringError(f"merge output chunk of extent {list(dst[0].extent)} does not match its role")
+    row = np.zeros((), dtype=nat.MERGE_TASK_DTYPE)
+    for name, pair in (("lo", lo), ("hi", hi), ("dst", dst)):
+        if pair is None:
+            continue
+        row[f"{name}_base"] = pair[0].base
+        row[f"{name}_idx_base"] = pair[1].base if pair[1] is not None else 0
+    row["rows"], row["na"], row["nb"] = rows, na, nb
+    row["lo_row_stride"], row["hi_row_stride"] = na, nb
+    row["dst_row_stride"] = nb if role == nat.MERGE_HIGH else na
+    row["role"] = role
+    return row
+
+
+def sort_work(rows: np.ndarray, tile: int) -> int:
+    """The most tile-sort workgroups any SORT_TASK_DTYPE row needs."""
+    work = 0
+    for r, n in zip(rows["rows"].tolist(), rows["n"].tolist()):
+        if r == 0 or n == 0:
+            continue
+        if n <= tile:
+            npad = 1 << (n - 1).bit_length()
+            work = max(work, -(-r * npad // tile))
+        else:
+            work = max(work, r * -(-n // tile))
+    return work
+
+
+class SortLaunch:
+    """One cubed_sort_chunks (``kind="chunk"``: the tile sort and the merge
+    passes inside every chunk, whose scratch ``alloc(nbytes) -> address``
+    provides) or cubed_merge_split (``kind="merge"``) launch over a device
+    table of one task per output chunk.  ``sink``: the list of buffers the
+    cache entry being built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, kind: str, ktype: int, descending: bool, pairs: bool, device,
+                 sink=None, alloc=None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.kind, self.ktype = kind, ktype
+        self.descending, self.pairs = bool(descending), bool(pairs)
+        self.flags = (nat.SORT_DESCENDING if descending else 0) | (nat.SORT_PAIRS if pairs else 0)
+        self.passes, self.scratch_bytes, self.work = 0, 0, 0
+        if self.ntasks == 0:
+            return
+        tile = nat.sort_tile()
+        if kind == "chunk":
+            self.passes, self.scratch_bytes = nat.sort_plan(rows, ktype, pairs)
+            self.work = sort_work(rows, tile)
+            if self.passes:
+                isz = 4 if ktype in (ir.dtype_code(np.float32), ir.dtype_code(np.int32),
+                                     ir.dtype_code(np.uint32)) else 8
+                at = alloc(self.scratch_bytes)
+                for row in rows:
+                    elems = int(row["rows"]) * int(row["dst_row_stride"])
+                    if elems == 0:
+                        continue
+                    row["scratch_base"] = at
+                    at += -(-elems * isz // 256) * 256
+                    if pairs:
+                        row["scratch_idx_base"] = at
+                        at += -(-elems * 8 // 256) * 256
+        else:
+            count = np.where(rows["role"] == nat.MERGE_HIGH, rows["nb"], rows["na"])
+            self.work = int((-(-(rows["rows"] * count) // tile)).max())
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0 or self.work == 0:
+            return
+        if self.kind == "chunk":
+            nat.check(nat.lib().cubed_sort_chunks(self.table.data_ptr(), self.ntasks, self.ktype, self.flags,
+                                                  self.passes, self.work, stream), "cubed_sort_chunks")
+        else:
+            nat.check(nat.lib().cubed_merge_split(self.table.data_ptr(), self.ntasks, self.ktype, self.flags,
+                                                  self.work, stream), "cubed_merge_split")
+
+
 # ------------------------------------------------------------------ programs
 
 

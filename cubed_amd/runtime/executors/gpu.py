@@ -46,6 +46,7 @@ from ...lowering import (
     LoweringError,
     Lowerer,
     ScanLaunch,
+    SortLaunch,
     _OffsetsSource,
     boxes_for_region,
     chunk_view,
@@ -394,7 +395,7 @@ class GpuDagExecutor(DagExecutor):
                     f"op {name}: {program.func!r} cannot run on the MI355X executor "
                     "(not expressible as a fused chunk program)")
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
-                                    ir.PerBlockProgram, ir.ScanProgram)):
+                                    ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -437,6 +438,9 @@ class GpuDagExecutor(DagExecutor):
             return self._lower_local(program, cfg, target, keys)
         if isinstance(program, ir.ScanProgram):
             raise LoweringError("cumulative_sum runs on one GPU only: its scan launches are not "
+                                f"lowered for a world of {self.world} ranks")
+        if isinstance(program, ir.SortProgram):
+            raise LoweringError("sort runs on one GPU only: its sort and merge launches are not "
                                 f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
@@ -591,6 +595,8 @@ class GpuDagExecutor(DagExecutor):
                 return split_launches(self, program, cfg, target, keys)
         if isinstance(program, ir.ScanProgram):
             return [self._lower_scan(program, cfg, target, keys)]
+        if isinstance(program, ir.SortProgram):
+            return [self._lower_sort(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -741,6 +747,55 @@ class GpuDagExecutor(DagExecutor):
             rows[i] = scan_task(views[0], chunk_view(target, key), axis,
                                 views[1] if program.carry else None, key[axis])
         return ScanLaunch(rows, vtype, program.exclusive, self.device, self._sink)
+
+    def _lower_sort(self, program, cfg, target, keys):
+        """One sort or merge task per output chunk (ir.SortProgram).  Every
+        task reads whole compact single chunks: one (``"chunk"``, or a
+        ``"merge"`` block without a partner, which is copied) or two (the lower
+        chunk of the pair first).  Pairs arrays are structured {v, i}, one slab
+        per field; a pairs chunk op reads plain keys."""
+        from ...lowering import merge_task, sort_ktype, sort_task
+
+        ktype = sort_ktype(program.dtype)
+        axis, pairs = program.axis, program.pairs
+        work_dtype = ir.sort_pairs_dtype(program.dtype) if pairs else np.dtype(program.dtype)
+        if np.dtype(target.dtype) != work_dtype:
+            raise LoweringError(f"sort of {program.dtype} keys into a {target.dtype} array")
+        merge = program.kind == "merge"
+        in_dtype = work_dtype if merge else np.dtype(program.dtype)
+
+        def views(arr, coords, structured):
+            if structured:
+                return chunk_view(arr, coords, "v"), chunk_view(arr, coords, "i")
+            return chunk_view(arr, coords), None
+
+        rows = np.zeros(len(keys), dtype=nat.MERGE_TASK_DTYPE if merge else nat.SORT_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            ins = []
+            for a in args:
+                if not isinstance(a, tuple):
+                    raise LoweringError("a sort task reads whole single chunks only")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != in_dtype:
+                    raise LoweringError(f"sort input {a[0]} is not a device array of {in_dtype}")
+                ins.append((tuple(a[1:]), views(src, a[1:], pairs and merge)))
+            out = views(target, key, pairs)
+            if not merge:
+                if len(ins) != 1:
+                    raise LoweringError(f"sort program with {len(ins)} inputs")
+                rows[i] = sort_task(ins[0][1][0], out[0], axis, target.chunk_start(key)[axis], out[1])
+            elif len(ins) == 1:
+                rows[i] = merge_task(ins[0][1], None, out, axis, nat.MERGE_COPY)
+            elif len(ins) == 2:
+                role = nat.MERGE_LOW if ins[0][0] == tuple(key) else nat.MERGE_HIGH
+                if ins[role][0] != tuple(key):  # MERGE_LOW = 0: own chunk first
+                    raise LoweringError(f"merge task {key} does not read its own chunk")
+                rows[i] = merge_task(ins[0][1], ins[1][1], out, axis, role)
+            else:
+                raise LoweringError(f"merge program with {len(ins)} inputs")
+        return SortLaunch(rows, program.kind, ktype, program.descending, pairs, self.device, self._sink,
+                          self.scratch)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""

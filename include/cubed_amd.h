@@ -38,6 +38,10 @@
  *   cubed_scan_chunks    -> no reference interface: Array API cumulative_sum
  *                           (2023.12) is not in v0.12.0; the semantics are
  *                           numpy's cumsum along one axis of a chunk.
+ *   cubed_sort_chunks,
+ *   cubed_merge_split    -> no reference interface: sort / argsort are listed
+ *                           as missing in the reference's api_status.md; the
+ *                           semantics are numpy's stable sort along one axis.
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -48,7 +52,7 @@
 extern "C" {
 #endif
 
-#define CUBED_ABI_VERSION 18
+#define CUBED_ABI_VERSION 19
 
 #define CUBED_MAX_DIMS 6   /* iteration dims of one task after coalescing   */
 #define CUBED_MAX_LEAVES 4 /* array/philox/const-array inputs of a program  */
@@ -418,6 +422,71 @@ int cubed_scan_path(const cubed_scan_task_t* tasks, int64_t ntasks, int32_t vtyp
  * its host copy. */
 int cubed_scan_chunks(const cubed_scan_task_t* d_tasks, int64_t ntasks, int32_t vtype,
                       int32_t exclusive, int32_t path, int64_t work, void* stream);
+
+/* Sorting along the last (contiguous) axis of a chunk (sort / argsort, ABI 19).
+ * A task is one chunk seen as (rows, n).  Keys are f32, f64, i32, i64, u32 or
+ * u64 (ktype: the cubed_dtype code).  Order: values ascend, every NaN is
+ * greater than every number and all NaNs tie, -0.0 and 0.0 tie; descending
+ * reverses the value order.  Pairs mode sorts (key, int64 index) with ties
+ * going to the smaller index in both directions, so its order is total and the
+ * result stable; keys-only mode leaves equal keys interchangeable.  No
+ * workgroup waits for, signals or reads the output of another one inside a
+ * launch; passes are ordered by the stream only. */
+#define CUBED_SORT_TILE 2048      /* elements one workgroup sorts in LDS */
+#define CUBED_SORT_DESCENDING 1   /* flags */
+#define CUBED_SORT_PAIRS 2
+
+/* cubed_sort_chunks task.  The tile sort reads src (keys only: in pairs mode
+ * element i of a row gets index index_base + i) and the merge passes ping-pong
+ * between dst and scratch, ending in dst.  Scratch buffers have dst's layout
+ * (rows * dst_row_stride elements); they may be 0 when the launch has no merge
+ * pass.  The idx addresses are used in pairs mode only. */
+typedef struct {
+  int64_t src_base;                        /* device byte addresses */
+  int64_t dst_base, dst_idx_base;
+  int64_t scratch_base, scratch_idx_base;
+  int64_t rows, n;                         /* elements */
+  int64_t src_row_stride, dst_row_stride;  /* elements */
+  int64_t index_base;
+} cubed_sort_task_t;
+
+/* cubed_merge_split task: the rows of a lower chunk (rows x na) and an upper
+ * chunk (rows x nb), each row sorted, are merged row by row (ties go to the
+ * lower chunk) and dst receives the first na (CUBED_MERGE_LOW) or the last nb
+ * (CUBED_MERGE_HIGH) elements of every merged row.  CUBED_MERGE_COPY: no
+ * partner, dst = the lower chunk (hi_* unused). */
+#define CUBED_MERGE_LOW 0
+#define CUBED_MERGE_HIGH 1
+#define CUBED_MERGE_COPY 2
+typedef struct {
+  int64_t lo_base, lo_idx_base;
+  int64_t hi_base, hi_idx_base;
+  int64_t dst_base, dst_idx_base;
+  int64_t rows, na, nb;
+  int64_t lo_row_stride, hi_row_stride, dst_row_stride;  /* elements */
+  int64_t role;
+} cubed_merge_task_t;
+
+/* Host only: CUBED_SORT_TILE of the loaded library. */
+int64_t cubed_sort_tile(void);
+/* Host only (no device call): validates a HOST copy of a sort task table
+ * (scratch addresses are not looked at) and reports what its launch needs:
+ * *passes = merge passes = ceil(log2(ceil(n / TILE))) of the largest n, and
+ * *scratch_bytes = 0 without a pass, else the sum over the tasks of their key
+ * (and, pairs, index) scratch, each rounded up to 256 bytes.  Returns 0 or a
+ * negative CUBED_E_* code. */
+int cubed_sort_plan(const cubed_sort_task_t* tasks, int64_t ntasks, int32_t ktype,
+                    int32_t pairs, int32_t* passes, int64_t* scratch_bytes);
+/* 1 + passes launches over a DEVICE task table.  work = the most workgroups
+ * any task needs: ceil(rows * npad / TILE) with npad the next power of two at
+ * or above n when n <= TILE, else rows * ceil(n / TILE).  Neither synchronises
+ * nor allocates. */
+int cubed_sort_chunks(const cubed_sort_task_t* d_tasks, int64_t ntasks, int32_t ktype,
+                      int32_t flags, int32_t passes, int64_t work, void* stream);
+/* One launch over a DEVICE table of merge tasks.  work = the most
+ * ceil(rows * count / TILE) of any task, count the elements per row it writes. */
+int cubed_merge_split(const cubed_merge_task_t* d_tasks, int64_t ntasks, int32_t ktype,
+                      int32_t flags, int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
