@@ -127,6 +127,15 @@ MERGE_TASK_DTYPE = np.dtype([
 SORT_DESCENDING, SORT_PAIRS = 1, 2
 MERGE_LOW, MERGE_HIGH, MERGE_COPY = 0, 1, 2
 
+# cubed_search_task_t (one chunk of values searched in one sorted chunk)
+SEARCH_TASK_DTYPE = np.dtype([
+    ("sorted_base", np.int64), ("values_base", np.int64), ("acc_base", np.int64), ("dst_base", np.int64),
+    ("n_sorted", np.int64), ("n_values", np.int64),
+])
+SEARCH_RIGHT = 1
+SEARCH_LDS, SEARCH_SPLIT = 0, 1
+SEARCH_VALUES = 16384  # CUBED_SEARCH_VALUES: values one workgroup searches
+
 
 class NativeError(RuntimeError):
     pass
@@ -171,6 +180,12 @@ def lib():
     L.cubed_sort_chunks.restype = c_int
     L.cubed_merge_split.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p]
     L.cubed_merge_split.restype = c_int
+    L.cubed_search_tile.argtypes = []
+    L.cubed_search_tile.restype = c_int64
+    L.cubed_search_path.argtypes = [c_void_p, c_int64, c_int32]
+    L.cubed_search_path.restype = c_int
+    L.cubed_search_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_search_chunks.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -273,6 +288,7 @@ EXPORTED_SYMBOLS = (
     "cubed_gemm_dist_image_bytes", "cubed_gemm_dist_pack_a", "cubed_gemm_dist_b_bytes", "cubed_gemm_dist_pack_b",
     "cubed_gemm_dist_gemm", "cubed_scan_path", "cubed_scan_chunks",
     "cubed_sort_tile", "cubed_sort_plan", "cubed_sort_chunks", "cubed_merge_split",
+    "cubed_search_tile", "cubed_search_path", "cubed_search_chunks",
 )
 
 
@@ -298,6 +314,21 @@ def sort_plan(rows: np.ndarray, ktype: int, pairs: bool):
     check(lib().cubed_sort_plan(rows.ctypes.data, len(rows), ktype, int(bool(pairs)),
                                 ctypes.byref(passes), ctypes.byref(nbytes)), "cubed_sort_plan")
     return passes.value, nbytes.value
+
+
+def search_tile() -> int:
+    """The most elements of a sorted chunk one workgroup of the search stages
+    whole in LDS (host only)."""
+    return int(lib().cubed_search_tile())
+
+
+def search_path(rows: np.ndarray, ktype: int) -> int:
+    """The kernel a host table of SEARCH_TASK_DTYPE rows takes (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=SEARCH_TASK_DTYPE)
+    path = lib().cubed_search_path(rows.ctypes.data, len(rows), ktype)
+    if path < 0:
+        check(path, "cubed_search_path")
+    return path
 
 
 INCLUDE_DIRS = ";".join([os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"),

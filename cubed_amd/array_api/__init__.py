@@ -54,7 +54,7 @@ from .manipulation_functions import (
     squeeze,
     stack,
 )
-from .searching_functions import argmax, argmin, where
+from .searching_functions import argmax, argmin, searchsorted, where
 from .sorting_functions import argsort, sort
 from .statistical_functions import cumulative_sum, max, mean, min, prod, std, sum, var
 from .utility_functions import all, any

@@ -11,6 +11,7 @@ from .ops import (
     rechunk,
     reduction,
     scan,
+    searchsorted,
     sort,
     sort_network,
     squeeze,
@@ -24,6 +25,6 @@ from .plan import Plan
 __all__ = [
     "CoreArray", "Plan", "blockwise", "compute", "elemwise", "from_array", "from_zarr",
     "gensym", "map_blocks", "map_direct", "measure_reserved_mem", "merge_chunks",
-    "partial_reduce", "rechunk", "reduction", "scan", "sort", "sort_network", "squeeze", "store", "to_zarr", "tree_reduce",
+    "partial_reduce", "rechunk", "reduction", "scan", "searchsorted", "sort", "sort_network", "squeeze", "store", "to_zarr", "tree_reduce",
     "unify_chunks", "visualize",
 ]

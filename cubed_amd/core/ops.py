@@ -912,6 +912,49 @@ def sort(x: "Array", axis: int, descending: bool = False, pairs: bool = False) -
     return cur
 
 
+# ------------------------------------------------------------------ searches
+
+
+class _search_block_function:
+    """Output block ``j`` of the search against block ``b`` of the sorted
+    array reads chunk ``j`` of the values, chunk ``b`` of the sorted array and,
+    after the first block, chunk ``j`` of the counts so far."""
+
+    def __init__(self, values_name, sorted_name, b, counts_name=None):
+        self.values_name, self.sorted_name, self.b, self.counts_name = values_name, sorted_name, b, counts_name
+
+    def __call__(self, out_key):
+        coords = tuple(out_key[1:])
+        keys = [(self.values_name,) + coords, (self.sorted_name, self.b)]
+        if self.counts_name is not None:
+            keys.append((self.counts_name,) + coords)
+        return keys
+
+
+def searchsorted(x1: "Array", x2: "Array", right: bool = False) -> "Array":
+    """For every element of ``x2`` the int64 number of elements of the sorted
+    1-d ``x1`` that sort before it (before or tied with it: ``right``), with
+    the shape and chunks of ``x2``.  Both have the same dtype, one of the sort
+    key types, and neither is empty.
+
+    The count over ``x1`` is the sum of the counts over its blocks, so with
+    ``nb`` blocks of ``x1`` the plan is ``nb`` chained ops: op ``b`` adds the
+    count against block ``b`` to the counts of op ``b - 1``.  A task reads one
+    chunk of ``x2``, one chunk of ``x1`` and (after the first op) one chunk of
+    counts, never more, and every op passes the ordinary projected-memory
+    check.  The price is ``nb`` passes over ``x2``: one read of its values
+    and one read and one write of the counts per block of ``x1``."""
+    dtype = np.dtype(x1.dtype)
+    counts = None
+    for b in range(x1.numblocks[0]):
+        args = (x2, x1) if counts is None else (x2, x1, counts)
+        counts = general_blockwise(
+            ir.SearchProgram(right=bool(right), dtype=dtype, nargs=len(args)),
+            _search_block_function(x2.name, x1.name, b, None if counts is None else counts.name),
+            *args, shape=x2.shape, dtype=np.int64, chunks=x2.chunks, extra_projected_mem=0, fusable=False)
+    return counts
+
+
 def _normalize_split_every(split_every, axis):
     split_every = split_every or 4
     if isinstance(split_every, dict):

@@ -26,6 +26,7 @@
 #include <limits>
 #include <stdio.h>
 #include "common.h"
+#include "sort_keys.h"
 
 namespace cubed {
 extern thread_local char g_err[512];
@@ -40,15 +41,7 @@ constexpr int kTile = CUBED_SORT_TILE;
 constexpr int kPer = kTile / kBlock;  // consecutive elements of one lane
 static_assert(kPer == 8, "the register steps are written for 8 elements per lane");
 
-template <typename T>
-constexpr bool is_float_key = is_same_v<T, float> || is_same_v<T, double>;
-
-// a sorts before b (ascending)
-template <typename T>
-CUBED_DEV bool key_lt(T a, T b) {
-  if constexpr (is_float_key<T>) return a < b || (b != b && a == a);
-  else return a < b;
-}
+// key_lt, is_float_key: sort_keys.h
 template <typename T>
 CUBED_DEV bool key_before(T a, T b, bool desc) { return desc ? key_lt(b, a) : key_lt(a, b); }
 

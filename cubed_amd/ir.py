@@ -458,6 +458,22 @@ class SortProgram(Program):
     name: str = "sort"
 
 
+@dataclass(frozen=True, eq=False)
+class SearchProgram(Program):
+    """Per task (searchsorted): for every element of one chunk of argument 0
+    (the values, any shape) the number of elements of one chunk of argument 1
+    (a block of the sorted 1-d array) that sort before it -- before or tied
+    with it when ``right`` -- in the order of ``SortProgram``, as int64.  With
+    ``nargs=3`` argument 2 is the int64 chunk of the counts over the earlier
+    blocks of the sorted array, which is added.  ``dtype`` is the common key
+    type of arguments 0 and 1 (float32, float64, a 32- or 64-bit integer).  Not
+    an expression program: never fused, and the rewrites leave it alone."""
+    right: bool = False
+    dtype: np.dtype = np.dtype("float64")
+    nargs: int = 2
+    name: str = "searchsorted"
+
+
 def sort_pairs_dtype(dtype) -> np.dtype:
     """Element type of the arrays a pairs-mode sort works on."""
     return np.dtype([("v", np.dtype(dtype)), ("i", np.int64)])

@@ -523,6 +523,61 @@ class SortLaunch:
                                                   self.work, stream), "cubed_merge_split")
 
 
+# ------------------------------------------------------------------ searches
+
+
+def search_task(sorted_view: ArrView, values: ArrView, dst: ArrView, acc: Optional[ArrView] = None):
+    """One nat.SEARCH_TASK_DTYPE row: the chunk view ``values`` (any shape)
+    searched in the 1-d sorted chunk view ``sorted_view`` into the int64 view
+    ``dst`` of the same extent, on top of the int64 counts ``acc`` if given.
+    All views are compact and C-ordered, so values and counts are flat runs."""
+    for v in (sorted_view, values, dst, acc):
+        if v is not None and list(v.stride) != list(c_strides(list(v.extent))):
+            raise LoweringError("searchsorted chunks must be compact and C-ordered")
+    if len(sorted_view.extent) != 1:
+        raise LoweringError(f"searchsorted looks in a 1-d chunk, not one of extent {list(sorted_view.extent)}")
+    if np.dtype(sorted_view.dtype) != np.dtype(values.dtype):
+        raise LoweringError(f"searchsorted of {values.dtype} values in {sorted_view.dtype} keys")
+    for v in (dst, acc):
+        if v is not None and (np.dtype(v.dtype) != np.int64 or list(v.extent) != list(values.extent)):
+            raise LoweringError(f"searchsorted counts chunk ({v.dtype}, extent {list(v.extent)}) does not match "
+                                f"its values chunk of extent {list(values.extent)}")
+    row = np.zeros((), dtype=nat.SEARCH_TASK_DTYPE)
+    row["sorted_base"], row["values_base"], row["dst_base"] = sorted_view.base, values.base, dst.base
+    row["acc_base"] = acc.base if acc is not None else 0
+    row["n_sorted"], row["n_values"] = sorted_view.extent[0], math.prod(values.extent)
+    return row
+
+
+class SearchLaunch:
+    """One cubed_search_chunks launch: a device table of search tasks (one per
+    output chunk).  The path is chosen once for the whole table, on the host
+    (cubed_search_path).  ``sink``: the list of buffers the cache entry being
+    built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, ktype: int, right: bool, device, sink=None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.ktype = ktype
+        self.right = bool(right)
+        self.flags = nat.SEARCH_RIGHT if right else 0
+        if self.ntasks == 0:
+            return
+        self.path = nat.search_path(rows, ktype)
+        self.work = int(-(-int(rows["n_values"].max()) // nat.SEARCH_VALUES))
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0 or self.work == 0:
+            return
+        nat.check(nat.lib().cubed_search_chunks(self.table.data_ptr(), self.ntasks, self.ktype, self.flags,
+                                                self.path, self.work, stream), "cubed_search_chunks")
+
+
 # ------------------------------------------------------------------ programs
 
 

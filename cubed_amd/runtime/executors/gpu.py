@@ -46,6 +46,7 @@ from ...lowering import (
     LoweringError,
     Lowerer,
     ScanLaunch,
+    SearchLaunch,
     SortLaunch,
     _OffsetsSource,
     boxes_for_region,
@@ -395,7 +396,8 @@ class GpuDagExecutor(DagExecutor):
                     f"op {name}: {program.func!r} cannot run on the MI355X executor "
                     "(not expressible as a fused chunk program)")
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
-                                    ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram)):
+                                    ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram,
+                                    ir.SearchProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -441,6 +443,9 @@ class GpuDagExecutor(DagExecutor):
                                 f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.SortProgram):
             raise LoweringError("sort runs on one GPU only: its sort and merge launches are not "
+                                f"lowered for a world of {self.world} ranks")
+        if isinstance(program, ir.SearchProgram):
+            raise LoweringError("searchsorted runs on one GPU only: its search launches are not "
                                 f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
@@ -597,6 +602,8 @@ class GpuDagExecutor(DagExecutor):
             return [self._lower_scan(program, cfg, target, keys)]
         if isinstance(program, ir.SortProgram):
             return [self._lower_sort(program, cfg, target, keys)]
+        if isinstance(program, ir.SearchProgram):
+            return [self._lower_search(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -796,6 +803,32 @@ class GpuDagExecutor(DagExecutor):
                 raise LoweringError(f"merge program with {len(ins)} inputs")
         return SortLaunch(rows, program.kind, ktype, program.descending, pairs, self.device, self._sink,
                           self.scratch)
+
+    def _lower_search(self, program, cfg, target, keys):
+        """One search task per output chunk (ir.SearchProgram): the chunk of
+        the values with the output chunk's extent, one chunk of the sorted
+        array and, with three arguments, the chunk of the counts so far."""
+        from ...lowering import search_task, sort_ktype
+
+        ktype = sort_ktype(program.dtype)
+        if np.dtype(target.dtype) != np.int64:
+            raise LoweringError(f"searchsorted counts into a {target.dtype} array")
+        rows = np.zeros(len(keys), dtype=nat.SEARCH_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            if len(args) != program.nargs or program.nargs not in (2, 3):
+                raise LoweringError(f"searchsorted program with {len(args)} inputs")
+            views = []
+            for a, dt in zip(args, (program.dtype, program.dtype, np.int64)):
+                if not isinstance(a, tuple):
+                    raise LoweringError("a searchsorted task reads whole single chunks only")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != np.dtype(dt):
+                    raise LoweringError(f"searchsorted input {a[0]} is not a device array of {np.dtype(dt)}")
+                views.append(chunk_view(src, a[1:]))
+            rows[i] = search_task(views[1], views[0], chunk_view(target, key),
+                                  views[2] if program.nargs == 3 else None)
+        return SearchLaunch(rows, ktype, program.right, self.device, self._sink)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""

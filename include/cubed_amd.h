@@ -42,6 +42,9 @@
  *   cubed_merge_split    -> no reference interface: sort / argsort are listed
  *                           as missing in the reference's api_status.md; the
  *                           semantics are numpy's stable sort along one axis.
+ *   cubed_search_chunks  -> no reference interface: searchsorted is not in the
+ *                           reference either; the semantics are numpy's
+ *                           searchsorted of a chunk of values in a sorted chunk.
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -487,6 +490,44 @@ int cubed_sort_chunks(const cubed_sort_task_t* d_tasks, int64_t ntasks, int32_t 
  * ceil(rows * count / TILE) of any task, count the elements per row it writes. */
 int cubed_merge_split(const cubed_merge_task_t* d_tasks, int64_t ntasks, int32_t ktype,
                       int32_t flags, int64_t work, void* stream);
+
+/* Searching a sorted chunk (searchsorted; new symbols only, the ABI version is
+ * unchanged).  A task counts, for every element v of a flat run of n_values
+ * values, the elements of a sorted run of n_sorted keys that sort before v
+ * (before or tied with v: CUBED_SEARCH_RIGHT) in the order of the sort
+ * entries: values ascend, every NaN is greater than every number and all NaNs
+ * tie, -0.0 and 0.0 tie.  dst[i] = (acc_base ? acc[i] : 0) + count(values[i]),
+ * int64; acc and dst are flat runs of n_values int64.  Keys and values have
+ * the same type (ktype: the cubed_dtype code of f32, f64, i32, i64, u32 or
+ * u64).  No workgroup waits for, signals or reads the output of another one
+ * and there are no atomics: results are bit-identical run to run. */
+#define CUBED_SEARCH_TILE 4096    /* most sorted elements one workgroup stages whole in
+                                     LDS (32 KiB at 8-byte keys); splitters of the other path */
+#define CUBED_SEARCH_VALUES 16384 /* values one workgroup searches */
+#define CUBED_SEARCH_RIGHT 1      /* flags */
+#define CUBED_SEARCH_LDS 0        /* paths: every n_sorted <= TILE, the sorted chunk in LDS */
+#define CUBED_SEARCH_SPLIT 1      /* up to TILE splitters in LDS, then one bucket in global memory */
+
+typedef struct {
+  int64_t sorted_base, values_base;  /* device byte addresses */
+  int64_t acc_base;                  /* 0 = none */
+  int64_t dst_base;
+  int64_t n_sorted, n_values;        /* elements */
+} cubed_search_task_t;
+
+/* Host only: CUBED_SEARCH_TILE of the loaded library. */
+int64_t cubed_search_tile(void);
+/* Host only (no device call): validates a HOST copy of a search task table and
+ * returns the path of its launch: CUBED_SEARCH_LDS when every task has
+ * n_sorted <= CUBED_SEARCH_TILE, else CUBED_SEARCH_SPLIT; a negative CUBED_E_*
+ * code for a malformed table. */
+int cubed_search_path(const cubed_search_task_t* tasks, int64_t ntasks, int32_t ktype);
+/* One launch over a DEVICE task table.  work = the most workgroups any task
+ * needs = ceil(n_values / CUBED_SEARCH_VALUES) of the largest n_values.
+ * CUBED_SEARCH_SPLIT is correct for every n_sorted, CUBED_SEARCH_LDS only for
+ * the tables cubed_search_path gives it to.  Neither synchronises nor allocates. */
+int cubed_search_chunks(const cubed_search_task_t* d_tasks, int64_t ntasks, int32_t ktype,
+                        int32_t flags, int32_t path, int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
