@@ -136,6 +136,13 @@ SEARCH_RIGHT = 1
 SEARCH_LDS, SEARCH_SPLIT = 0, 1
 SEARCH_VALUES = 16384  # CUBED_SEARCH_VALUES: values one workgroup searches
 
+# cubed_hist_task_t (one chunk of values counted into one row of bins)
+HIST_TASK_DTYPE = np.dtype([
+    ("x_base", np.int64), ("edges_base", np.int64), ("dst_base", np.int64), ("n_values", np.int64),
+])
+HIST_UNIFORM, HIST_SEARCH, HIST_WIDE = 0, 1, 2
+HIST_VALUES = 16384  # CUBED_HIST_VALUES: least values of a workgroup's share
+
 
 class NativeError(RuntimeError):
     pass
@@ -186,6 +193,12 @@ def lib():
     L.cubed_search_path.restype = c_int
     L.cubed_search_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
     L.cubed_search_chunks.restype = c_int
+    L.cubed_hist_bins_lds.argtypes = []
+    L.cubed_hist_bins_lds.restype = c_int64
+    L.cubed_hist_path.argtypes = [c_void_p, c_int64, c_int32, c_int64, c_int32]
+    L.cubed_hist_path.restype = c_int
+    L.cubed_hist_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int64, c_int32, c_int64, c_void_p]
+    L.cubed_hist_chunks.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -289,6 +302,7 @@ EXPORTED_SYMBOLS = (
     "cubed_gemm_dist_gemm", "cubed_scan_path", "cubed_scan_chunks",
     "cubed_sort_tile", "cubed_sort_plan", "cubed_sort_chunks", "cubed_merge_split",
     "cubed_search_tile", "cubed_search_path", "cubed_search_chunks",
+    "cubed_hist_bins_lds", "cubed_hist_path", "cubed_hist_chunks",
 )
 
 
@@ -328,6 +342,21 @@ def search_path(rows: np.ndarray, ktype: int) -> int:
     path = lib().cubed_search_path(rows.ctypes.data, len(rows), ktype)
     if path < 0:
         check(path, "cubed_search_path")
+    return path
+
+
+def hist_bins_lds() -> int:
+    """The most bins whose edges and counters one workgroup of the histogram
+    keeps in LDS (host only)."""
+    return int(lib().cubed_hist_bins_lds())
+
+
+def hist_path(rows: np.ndarray, ktype: int, nbins: int, uniform: bool) -> int:
+    """The kernel a host table of HIST_TASK_DTYPE rows takes (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=HIST_TASK_DTYPE)
+    path = lib().cubed_hist_path(rows.ctypes.data, len(rows), ktype, nbins, int(bool(uniform)))
+    if path < 0:
+        check(path, "cubed_hist_path")
     return path
 
 

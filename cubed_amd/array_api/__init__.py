@@ -56,5 +56,5 @@ from .manipulation_functions import (
 )
 from .searching_functions import argmax, argmin, searchsorted, where
 from .sorting_functions import argsort, sort
-from .statistical_functions import cumulative_sum, max, mean, min, prod, std, sum, var
+from .statistical_functions import cumulative_sum, histogram, max, mean, min, prod, std, sum, var
 from .utility_functions import all, any

@@ -127,6 +127,67 @@ def cumulative_sum(x, /, *, axis=None, dtype=None, include_initial=False):
     return astype(result, dtype, copy=False)
 
 
+def histogram(x, /, bins, *, range=None, density=False, weights=None):
+    """``np.histogram`` of all elements of ``x`` (any shape and chunking):
+    ``(hist, bin_edges)``, both one-chunk arrays; ``hist`` is int64 of shape
+    ``(nbins,)``, or float64 with ``density=True``.
+
+    ``bins`` is an int, and then ``range=(lo, hi)`` is required because ``x``
+    is lazy and its extremes are not known, or a host 1-d array-like of
+    non-decreasing edges, and then ``range`` is ignored as numpy ignores it.
+    The edges are numpy's own, ``np.histogram_bin_edges`` of an empty array of
+    ``x``'s dtype, so their dtype (float32 for float32 ``x``, else float64), a
+    widened degenerate range and every ``ValueError`` are numpy's.  ``x`` is
+    converted to the edges' dtype and counted by numpy's definition: bin ``i``
+    holds ``e[i] <= v < e[i+1]``, the last bin also ``v == e[nbins]``; NaN and
+    values outside ``[e[0], e[nbins]]`` are counted nowhere.
+
+    The dtypes are those ``sort`` accepts.  ``weights`` is not supported: a
+    float sum per bin through atomics would depend on the order of arrival.
+    The reference has no histogram, so parity is unpinned; numpy is the
+    yardstick."""
+    from ..core.array import CoreArray
+    from ..core.ops import from_array
+    from ..core.ops import histogram as _histogram
+    from .creation_functions import zeros
+    from .data_type_functions import astype
+    from .elementwise_functions import divide, multiply
+    from .sorting_functions import _KEY_DTYPE
+
+    if np.dtype(x.dtype) not in _KEY_DTYPE:
+        raise TypeError("Only boolean, integer, float32 and float64 dtypes are allowed in histogram")
+    if weights is not None:
+        raise NotImplementedError("histogram with weights is not supported: a float sum per bin through "
+                                  "atomics depends on the order of arrival")
+    if isinstance(bins, CoreArray):
+        raise TypeError("histogram: bins must be an int or a host array of edges; compute() the array first")
+    uniform = np.ndim(bins) == 0
+    if uniform and range is None:
+        raise ValueError("histogram: range=(lo, hi) is required with an int bins, because x is lazy and "
+                         "its minimum and maximum are not known")
+    # numpy itself counts bool as uint8 (and says so in a warning that is no news here)
+    like = np.empty(0, dtype=np.uint8 if x.dtype == np.bool_ else x.dtype)
+    edges = np.histogram_bin_edges(like, bins, range if uniform else None)
+    nbins = len(edges) - 1
+    if nbins < 1:
+        raise ValueError("histogram: bins must hold at least two edges")
+    bin_edges = from_array(edges, chunks=edges.shape, spec=x.spec)
+    if x.size == 0:
+        hist = zeros((nbins,), dtype=int64, chunks=(nbins,), spec=x.spec)
+    else:
+        # explicit edges keep the dtype they came with; the comparison runs in float32 only
+        # where both sides are float32, else in float64 as numpy's promotion has it
+        key_dtype = float32 if edges.dtype == x.dtype == np.dtype(float32) else float64
+        key_edges = bin_edges if edges.dtype == np.dtype(key_dtype) else \
+            from_array(edges.astype(key_dtype), chunks=edges.shape, spec=x.spec)
+        hist = _histogram(x, key_edges, nbins, uniform)
+    if density:
+        widths = from_array(np.diff(edges).astype(np.float64), chunks=(nbins,), spec=x.spec)
+        counts = astype(hist, float64)
+        hist = divide(counts, multiply(sum(counts), widths))
+    return hist, bin_edges
+
+
 def _var_std(x, axis, correction, keepdims, use_new_impl, sqrt):
     if x.dtype not in _real_floating_dtypes:
         raise TypeError(f"Only real floating-point dtypes are allowed in {'std' if sqrt else 'var'}")

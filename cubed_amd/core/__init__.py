@@ -4,6 +4,7 @@ from .ops import (
     elemwise,
     from_array,
     from_zarr,
+    histogram,
     map_blocks,
     map_direct,
     merge_chunks,
@@ -24,7 +25,7 @@ from .plan import Plan
 
 __all__ = [
     "CoreArray", "Plan", "blockwise", "compute", "elemwise", "from_array", "from_zarr",
-    "gensym", "map_blocks", "map_direct", "measure_reserved_mem", "merge_chunks",
+    "gensym", "histogram", "map_blocks", "map_direct", "measure_reserved_mem", "merge_chunks",
     "partial_reduce", "rechunk", "reduction", "scan", "searchsorted", "sort", "sort_network", "squeeze", "store", "to_zarr", "tree_reduce",
     "unify_chunks", "visualize",
 ]

@@ -955,6 +955,53 @@ def searchsorted(x1: "Array", x2: "Array", right: bool = False) -> "Array":
     return counts
 
 
+# ------------------------------------------------------------------ histograms
+
+
+class _hist_block_function:
+    """Output block ``(b..., 0)`` of the partial histograms reads chunk
+    ``b...`` of the values and the one chunk of the edges."""
+
+    def __init__(self, x_name, edges_name):
+        self.x_name, self.edges_name = x_name, edges_name
+
+    def __call__(self, out_key):
+        return [(self.x_name,) + tuple(out_key[1:-1]), (self.edges_name, 0)]
+
+
+def histogram(x: "Array", edges: "Array", nbins: int, uniform: bool) -> "Array":
+    """The int64 counts, shape ``(nbins,)`` in one chunk, of the elements of
+    ``x`` (any shape, not empty) in the bins of the 1-d one-chunk array
+    ``edges`` of ``nbins + 1`` non-decreasing values (``ir.HistogramProgram``);
+    ``uniform`` says that the edges are evenly spaced.
+
+    ``x`` is converted to the edges' dtype first (float32 only for float32 ``x``
+    with float32 edges, else float64), so the kernel has two key types; for
+    non-float ``x`` that is one extra pass.  Then one op counts every chunk of
+    ``x`` into its own row of a partials array of shape ``x.numblocks +
+    (nbins,)`` -- a task reads one chunk of ``x`` and the edges and writes
+    ``nbins`` counts, which the ordinary projected-memory check covers -- and
+    the existing sum reduction adds the rows up."""
+    from ..array_api import astype
+    from ..array_api.statistical_functions import sum as _sum
+
+    dtype = np.dtype(edges.dtype)
+    if edges.ndim != 1 or edges.numblocks != (1,) or edges.shape[0] != nbins + 1 or nbins < 1:
+        raise ValueError(f"histogram: {nbins} bins need one chunk of {nbins + 1} edges")
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"histogram: edges of dtype {dtype}")
+    x = astype(x, dtype, copy=False)
+    shape = tuple(x.numblocks) + (nbins,)
+    chunks = tuple((1,) * n for n in x.numblocks) + ((nbins,),)
+    partials = general_blockwise(
+        ir.HistogramProgram(nbins=int(nbins), uniform=bool(uniform), dtype=dtype, nargs=2),
+        _hist_block_function(x.name, edges.name),
+        x, edges, shape=shape, dtype=np.int64, chunks=chunks, extra_projected_mem=0, fusable=False)
+    if x.ndim == 0:
+        return partials
+    return _sum(partials, axis=tuple(range(x.ndim)), dtype=np.int64)
+
+
 def _normalize_split_every(split_every, axis):
     split_every = split_every or 4
     if isinstance(split_every, dict):

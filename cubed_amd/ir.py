@@ -474,6 +474,23 @@ class SearchProgram(Program):
     name: str = "searchsorted"
 
 
+@dataclass(frozen=True, eq=False)
+class HistogramProgram(Program):
+    """Per task (histogram): the int64 counts of one chunk of argument 0 (the
+    values, any shape) in the ``nbins`` bins of the one chunk of argument 1
+    (the ``nbins + 1`` non-decreasing edges), numpy's definition: bin ``i``
+    holds ``e[i] <= v < e[i+1]``, the last bin also ``v == e[nbins]``.
+    ``uniform``: the edges are evenly spaced (they came from an int ``bins``),
+    which only chooses how a bin is looked for.  ``dtype`` is the common type
+    of both arguments (float32 or float64).  Not an expression program: never
+    fused, and the rewrites leave it alone."""
+    nbins: int = 1
+    uniform: bool = False
+    dtype: np.dtype = np.dtype("float64")
+    nargs: int = 2
+    name: str = "histogram"
+
+
 def sort_pairs_dtype(dtype) -> np.dtype:
     """Element type of the arrays a pairs-mode sort works on."""
     return np.dtype([("v", np.dtype(dtype)), ("i", np.int64)])

@@ -578,6 +578,85 @@ class SearchLaunch:
                                                 self.path, self.work, stream), "cubed_search_chunks")
 
 
+# ------------------------------------------------------------------ histograms
+
+HIST_GROUPS = 4096          # workgroups a launch aims at: two rounds of 8 per CU
+HIST_SHARE_MAX = 1 << 31    # most values of a workgroup's share; its 32-bit counters hold 2^32 - 1
+HIST_MAX_GROUPS = 2 ** 31 - 1
+
+
+def hist_task(x: ArrView, edges: ArrView, dst: ArrView, nbins: int):
+    """One nat.HIST_TASK_DTYPE row: the chunk view ``x`` (any shape) counted
+    into the int64 view ``dst``, whose last extent is ``nbins`` and whose other
+    extents are 1, over the ``nbins + 1`` edges of the 1-d view ``edges``.  All
+    views are compact and C-ordered, so the values are one flat run."""
+    for v in (x, edges, dst):
+        if list(v.stride) != list(c_strides(list(v.extent))):
+            raise LoweringError("histogram chunks must be compact and C-ordered")
+    if list(edges.extent) != [nbins + 1]:
+        raise LoweringError(f"histogram of {nbins} bins over an edges chunk of extent {list(edges.extent)}")
+    if np.dtype(edges.dtype) != np.dtype(x.dtype):
+        raise LoweringError(f"histogram of {x.dtype} values over {edges.dtype} edges")
+    if np.dtype(dst.dtype) != np.int64:
+        raise LoweringError(f"histogram counts into a {dst.dtype} chunk")
+    if not dst.extent or list(dst.extent) != [1] * (len(dst.extent) - 1) + [nbins]:
+        raise LoweringError(f"histogram counts chunk of extent {list(dst.extent)}, not (1, ..., {nbins})")
+    row = np.zeros((), dtype=nat.HIST_TASK_DTYPE)
+    row["x_base"], row["edges_base"], row["dst_base"] = x.base, edges.base, dst.base
+    row["n_values"] = math.prod(x.extent)
+    return row
+
+
+def hist_work(rows: np.ndarray, nbins: int, path: int) -> int:
+    """Workgroups per task of a histogram launch.  A workgroup's share of a
+    task is ceil(n_values / work) values: at least HIST_VALUES and, where it
+    stages and flushes ``nbins`` LDS counters, eight values per bin, so that
+    those are paid for; large enough that the table gives about HIST_GROUPS
+    workgroups; and at most HIST_SHARE_MAX, because the counters are 32 bits
+    wide.  LoweringError if that takes more workgroups than one grid has."""
+    n = rows["n_values"].astype(np.int64)
+    if len(n) == 0 or int(n.max()) == 0:
+        return 0
+    share = max(nat.HIST_VALUES, -(-int(n.sum()) // HIST_GROUPS))
+    if path != nat.HIST_WIDE:
+        share = max(share, 8 * int(nbins))
+    share = min(share, HIST_SHARE_MAX)
+    work = -(-int(n.max()) // share)
+    if work * len(n) > HIST_MAX_GROUPS:
+        raise LoweringError(f"histogram: {len(n)} tasks of up to {int(n.max())} values need {work * len(n)} "
+                            f"workgroups of at most {HIST_SHARE_MAX} values each, more than one launch has")
+    return work
+
+
+class HistLaunch:
+    """One cubed_hist_chunks launch: a device table of histogram tasks (one
+    per chunk of the values).  The path is chosen once for the whole table, on
+    the host (cubed_hist_path).  ``sink``: the list of buffers the cache entry
+    being built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, ktype: int, nbins: int, uniform: bool, device, sink=None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.ktype = ktype
+        self.nbins = int(nbins)
+        self.uniform = bool(uniform)
+        if self.ntasks == 0:
+            return
+        self.path = nat.hist_path(rows, ktype, self.nbins, self.uniform)
+        self.work = hist_work(rows, self.nbins, self.path)
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0:
+            return
+        nat.check(nat.lib().cubed_hist_chunks(self.table.data_ptr(), self.ntasks, self.ktype, self.nbins,
+                                              self.path, self.work, stream), "cubed_hist_chunks")
+
+
 # ------------------------------------------------------------------ programs
 
 

@@ -43,6 +43,7 @@ from ...lowering import (
     CopyLaunch,
     FusedLaunch,
     GemmLaunch,
+    HistLaunch,
     LoweringError,
     Lowerer,
     ScanLaunch,
@@ -397,7 +398,7 @@ class GpuDagExecutor(DagExecutor):
                     "(not expressible as a fused chunk program)")
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
                                     ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram,
-                                    ir.SearchProgram)):
+                                    ir.SearchProgram, ir.HistogramProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -446,6 +447,9 @@ class GpuDagExecutor(DagExecutor):
                                 f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.SearchProgram):
             raise LoweringError("searchsorted runs on one GPU only: its search launches are not "
+                                f"lowered for a world of {self.world} ranks")
+        if isinstance(program, ir.HistogramProgram):
+            raise LoweringError("histogram runs on one GPU only: its counting launches are not "
                                 f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
@@ -604,6 +608,8 @@ class GpuDagExecutor(DagExecutor):
             return [self._lower_sort(program, cfg, target, keys)]
         if isinstance(program, ir.SearchProgram):
             return [self._lower_search(program, cfg, target, keys)]
+        if isinstance(program, ir.HistogramProgram):
+            return [self._lower_hist(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -829,6 +835,35 @@ class GpuDagExecutor(DagExecutor):
             rows[i] = search_task(views[1], views[0], chunk_view(target, key),
                                   views[2] if program.nargs == 3 else None)
         return SearchLaunch(rows, ktype, program.right, self.device, self._sink)
+
+    def _lower_hist(self, program, cfg, target, keys):
+        """One histogram task per output chunk (ir.HistogramProgram): one whole
+        chunk of the values and the single chunk of the edges, counted into
+        the output chunk, a row of ``nbins`` int64."""
+        from ...lowering import hist_task
+
+        dtype = np.dtype(program.dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise LoweringError(f"histogram of {dtype} values is not lowered (float32, float64)")
+        if np.dtype(target.dtype) != np.int64:
+            raise LoweringError(f"histogram counts into a {target.dtype} array")
+        rows = np.zeros(len(keys), dtype=nat.HIST_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            if len(args) != 2 or program.nargs != 2:
+                raise LoweringError(f"histogram program with {len(args)} inputs")
+            views = []
+            for a in args:
+                if not isinstance(a, tuple):
+                    raise LoweringError("a histogram task reads whole single chunks only")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != dtype:
+                    raise LoweringError(f"histogram input {a[0]} is not a device array of {dtype}")
+                views.append(chunk_view(src, a[1:]))
+            if tuple(args[1][1:]) != (0,) or cfg.reads_map[args[1][0]].array.numblocks != (1,):
+                raise LoweringError("a histogram task reads the single chunk of its edges")
+            rows[i] = hist_task(views[0], views[1], chunk_view(target, key), program.nbins)
+        return HistLaunch(rows, ir.dtype_code(dtype), program.nbins, program.uniform, self.device, self._sink)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""

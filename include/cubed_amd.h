@@ -45,6 +45,9 @@
  *   cubed_search_chunks  -> no reference interface: searchsorted is not in the
  *                           reference either; the semantics are numpy's
  *                           searchsorted of a chunk of values in a sorted chunk.
+ *   cubed_hist_chunks    -> no reference interface: histogram is not in the
+ *                           reference either; the semantics are numpy's
+ *                           histogram of a chunk of values over given edges.
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -528,6 +531,50 @@ int cubed_search_path(const cubed_search_task_t* tasks, int64_t ntasks, int32_t 
  * the tables cubed_search_path gives it to.  Neither synchronises nor allocates. */
 int cubed_search_chunks(const cubed_search_task_t* d_tasks, int64_t ntasks, int32_t ktype,
                         int32_t flags, int32_t path, int64_t work, void* stream);
+
+/* Histogram of a chunk (histogram; new symbols only, the ABI version is
+ * unchanged).  A task counts a flat run of n_values values v into the nbins
+ * bins of nbins + 1 non-decreasing edges e, numpy's definition: bin i holds
+ * e[i] <= v < e[i+1], the last bin also v == e[nbins]; NaN and values outside
+ * [e[0], e[nbins]] are counted nowhere, -0.0 == 0.0, and a zero-width bin gets
+ * nothing unless it is the last.  Only comparisons with the edges decide a
+ * bin.  dst is the task's own row of nbins int64 counts; the entry zeroes every
+ * row on the stream before it counts.  Values and edges have the same type
+ * (ktype: CUBED_F32 or CUBED_F64).  A workgroup counts its share of a task,
+ * ceil(n_values / work) rounded up to 1024 values, in 32-bit LDS counters (or
+ * not at all: CUBED_HIST_WIDE) and adds them to dst with 64-bit integer
+ * atomics, so the share must stay below 2^32; integer sums do not depend on
+ * their order and results are bit-identical run to run. */
+#define CUBED_HIST_BINS_LDS 4096 /* most bins whose edges and counters one workgroup keeps in
+                                    LDS: 48 KiB at 8-byte edges, three workgroups per CU */
+#define CUBED_HIST_VALUES 16384  /* least values of a workgroup's share the host plans with */
+#define CUBED_HIST_UNIFORM 0     /* paths: nbins <= BINS_LDS, evenly spaced edges: a guessed
+                                    bin corrected against the edges in LDS */
+#define CUBED_HIST_SEARCH 1      /* nbins <= BINS_LDS: binary search of the edges in LDS */
+#define CUBED_HIST_WIDE 2        /* any nbins: binary search of the edges in global memory, one
+                                    64-bit atomic per run of equal bins of a wave */
+
+typedef struct {
+  int64_t x_base, edges_base, dst_base; /* device byte addresses */
+  int64_t n_values;                     /* elements of x */
+} cubed_hist_task_t;
+
+/* Host only: CUBED_HIST_BINS_LDS of the loaded library. */
+int64_t cubed_hist_bins_lds(void);
+/* Host only (no device call): validates a HOST copy of a histogram task table
+ * and returns the path of its launch: CUBED_HIST_WIDE when nbins >
+ * CUBED_HIST_BINS_LDS, else CUBED_HIST_UNIFORM if uniform (the edges are evenly
+ * spaced) and CUBED_HIST_SEARCH if not; a negative CUBED_E_* code for a
+ * malformed table. */
+int cubed_hist_path(const cubed_hist_task_t* tasks, int64_t ntasks, int32_t ktype, int64_t nbins,
+                    int32_t uniform);
+/* One zeroing launch and one counting launch over a DEVICE task table, grid
+ * ntasks x work workgroups.  CUBED_HIST_WIDE and CUBED_HIST_SEARCH are correct
+ * for every set of edges (the latter for nbins <= CUBED_HIST_BINS_LDS),
+ * CUBED_HIST_UNIFORM is as well but slow for edges far from evenly spaced.
+ * Neither synchronises nor allocates. */
+int cubed_hist_chunks(const cubed_hist_task_t* d_tasks, int64_t ntasks, int32_t ktype, int64_t nbins,
+                      int32_t path, int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
