@@ -143,6 +143,16 @@ HIST_TASK_DTYPE = np.dtype([
 HIST_UNIFORM, HIST_SEARCH, HIST_WIDE = 0, 1, 2
 HIST_VALUES = 16384  # CUBED_HIST_VALUES: least values of a workgroup's share
 
+# cubed_unique_task_t (one sorted chunk whose run heads are counted or packed)
+UNIQUE_TASK_DTYPE = np.dtype([
+    ("src_base", np.int64), ("src_idx_base", np.int64), ("prev_base", np.int64),
+    ("dst_base", np.int64), ("dst_idx_base", np.int64), ("scratch_base", np.int64),
+    ("n", np.int64), ("n_prev", np.int64), ("offset", np.int64),
+])
+UNIQUE_TILE = 4096  # CUBED_UNIQUE_TILE: elements of one workgroup
+UNIQUE_COUNT, UNIQUE_PACK = 0, 1
+UNIQUE_KEYS, UNIQUE_POSITION, UNIQUE_INDEX = 0, 1, 2
+
 
 class NativeError(RuntimeError):
     pass
@@ -199,6 +209,12 @@ def lib():
     L.cubed_hist_path.restype = c_int
     L.cubed_hist_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int64, c_int32, c_int64, c_void_p]
     L.cubed_hist_chunks.restype = c_int
+    L.cubed_unique_tile.argtypes = []
+    L.cubed_unique_tile.restype = c_int64
+    L.cubed_unique_work.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32]
+    L.cubed_unique_work.restype = c_int64
+    L.cubed_unique_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_unique_chunks.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -303,6 +319,7 @@ EXPORTED_SYMBOLS = (
     "cubed_sort_tile", "cubed_sort_plan", "cubed_sort_chunks", "cubed_merge_split",
     "cubed_search_tile", "cubed_search_path", "cubed_search_chunks",
     "cubed_hist_bins_lds", "cubed_hist_path", "cubed_hist_chunks",
+    "cubed_unique_tile", "cubed_unique_work", "cubed_unique_chunks",
 )
 
 
@@ -358,6 +375,22 @@ def hist_path(rows: np.ndarray, ktype: int, nbins: int, uniform: bool) -> int:
     if path < 0:
         check(path, "cubed_hist_path")
     return path
+
+
+def unique_tile() -> int:
+    """Elements of a sorted chunk one workgroup of the run-head kernels owns
+    (host only)."""
+    return int(lib().cubed_unique_tile())
+
+
+def unique_work(rows: np.ndarray, ktype: int, kind: int, payload: int) -> int:
+    """Validates a host table of UNIQUE_TASK_DTYPE rows and gives the
+    workgroups per task of its launch (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=UNIQUE_TASK_DTYPE)
+    work = int(lib().cubed_unique_work(rows.ctypes.data, len(rows), ktype, kind, payload))
+    if work < 0:
+        check(work, "cubed_unique_work")
+    return work
 
 
 INCLUDE_DIRS = ";".join([os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"),

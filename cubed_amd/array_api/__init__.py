@@ -55,6 +55,7 @@ from .manipulation_functions import (
     stack,
 )
 from .searching_functions import argmax, argmin, searchsorted, where
+from .set_functions import unique_all, unique_counts, unique_inverse, unique_values
 from .sorting_functions import argsort, sort
 from .statistical_functions import cumulative_sum, histogram, max, mean, min, prod, std, sum, var
 from .utility_functions import all, any

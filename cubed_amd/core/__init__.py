@@ -3,6 +3,7 @@ from .ops import (
     blockwise,
     elemwise,
     from_array,
+    from_device,
     from_zarr,
     histogram,
     map_blocks,
@@ -20,12 +21,15 @@ from .ops import (
     to_zarr,
     tree_reduce,
     unify_chunks,
+    unique_count,
+    unique_gather,
+    unique_pack,
 )
 from .plan import Plan
 
 __all__ = [
-    "CoreArray", "Plan", "blockwise", "compute", "elemwise", "from_array", "from_zarr",
+    "CoreArray", "Plan", "blockwise", "compute", "elemwise", "from_array", "from_device", "from_zarr",
     "gensym", "histogram", "map_blocks", "map_direct", "measure_reserved_mem", "merge_chunks",
     "partial_reduce", "rechunk", "reduction", "scan", "searchsorted", "sort", "sort_network", "squeeze", "store", "to_zarr", "tree_reduce",
-    "unify_chunks", "visualize",
+    "unify_chunks", "unique_count", "unique_gather", "unique_pack", "visualize",
 ]

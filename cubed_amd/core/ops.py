@@ -511,6 +511,7 @@ def map_direct(func, *args: "Array", shape, dtype, chunks, extra_projected_mem, 
     out = empty_virtual_array(shape, dtype=dtype, chunks=chunks, spec=spec)
     kwargs.pop("target_chunks", None)
     kwargs.pop("selection", None)
+    field = kwargs.pop("field", None)  # read one field of a structured source (concat regions only)
     ndim = len(shape)
     src = args[0]
     region_fn = func
@@ -531,7 +532,8 @@ def map_direct(func, *args: "Array", shape, dtype, chunks, extra_projected_mem, 
     def build(block_arg):
         if isinstance(region_fn, ConcatRegions):
             leaf = ir.Concat(src.name, np.dtype(dtype), tuple(range(ndim)), region_fn, block_arg,
-                             sources=tuple(a.zarray_maybe_lazy for a in args), axis=region_fn.axis)
+                             field=field, sources=tuple(a.zarray_maybe_lazy for a in args),
+                             axis=region_fn.axis)
         else:
             leaf = ir.Region(src.name, src.dtype, axes, region_fn, block_arg,
                              target=src.zarray_maybe_lazy)
@@ -572,6 +574,38 @@ class ConcatRegions:
                 region = list(base)
                 region[ax] = slice(pos - self.offsets[i], stop - self.offsets[i], 1)
                 parts.append((i, tuple(region), pos - lo))
+            pos = stop
+        return parts
+
+
+class GatherRegions(ConcatRegions):
+    """Regions read by output block ``j`` of ``unique_gather``: every piece
+    names the one source array (index 0).  Block ``b`` of the 1-d source, whose
+    chunks are ``in_chunks``, holds ``counts[b]`` wanted elements at its front;
+    the output is their concatenation, ``k = sum(counts)`` elements in chunks
+    of ``out_chunks``.  A piece is (0, region of the source, offset inside the
+    output block); blocks with a zero count contribute none."""
+
+    def __init__(self, out_chunks, in_chunks, counts):
+        ends = np.cumsum(np.asarray(counts, dtype=np.int64))
+        super().__init__(out_chunks, 0, [0] + [int(v) for v in ends])
+        self.in_starts = [0] + [int(v) for v in np.cumsum(np.asarray(in_chunks, dtype=np.int64))[:-1]]
+
+    def __call__(self, block_id):
+        from bisect import bisect
+
+        j = block_id[0]
+        lo = sum(self.out_chunks[0][:j])
+        hi = lo + self.out_chunks[0][j]
+        parts = []
+        pos = lo
+        while pos < hi:
+            # the last block whose first output position is <= pos: zero-count
+            # blocks share their start with the next one and are skipped
+            b = bisect(self.offsets, pos) - 1
+            stop = min(hi, self.offsets[b + 1])
+            at = self.in_starts[b] + pos - self.offsets[b]
+            parts.append((0, (slice(at, at + stop - pos, 1),), pos - lo))
             pos = stop
         return parts
 
@@ -874,7 +908,8 @@ class _merge_block_function:
         return [(self.name,) + lo, (self.name,) + hi]
 
 
-def sort(x: "Array", axis: int, descending: bool = False, pairs: bool = False) -> "Array":
+def sort(x: "Array", axis: int, descending: bool = False, pairs: bool = False,
+         return_pairs: bool = False) -> "Array":
     """``x`` sorted along ``axis`` (``pairs=False``, same dtype) or the int64
     indices that sort it (``pairs=True``), same shape and chunks.  ``x.dtype``
     is one of the sort key types (float32, float64, 32- and 64-bit integers).
@@ -885,12 +920,20 @@ def sort(x: "Array", axis: int, descending: bool = False, pairs: bool = False) -
     first one materialises, a sort is never fused).  One block along the axis:
     one ``"chunk"`` op.  ``nb`` blocks: the chunk op, then one ``"merge"`` op
     of ``nb`` tasks per round of ``sort_network(nb)``.  No task reads more
-    than two chunks; every op passes the ordinary projected-memory check."""
+    than two chunks; every op passes the ordinary projected-memory check.
+
+    ``return_pairs`` (with ``pairs``, and an axis that needs no permute): the
+    sorted ``ir.sort_pairs_dtype`` array ``{v, i}`` itself, keys next to their
+    indices, instead of the indices alone."""
     from ..array_api.manipulation_functions import permute_dims
     from ..chunkfuncs import _arg_aggregate
 
     nd = x.ndim
+    if return_pairs and not pairs:
+        raise ValueError("sort: return_pairs needs pairs")
     if builtins.any(s > 1 for s in x.shape[axis + 1:]):
+        if return_pairs:
+            raise ValueError("sort: return_pairs along an axis that is not the last one with more than one element")
         order = [d for d in range(nd) if d != axis] + [axis]
         y = sort(permute_dims(x, tuple(order)), nd - 1, descending, pairs)
         return permute_dims(y, tuple(int(i) for i in np.argsort(order)))
@@ -907,7 +950,7 @@ def sort(x: "Array", axis: int, descending: bool = False, pairs: bool = False) -
             ir.SortProgram(axis=axis, descending=descending, pairs=pairs, dtype=dtype, kind="merge", nargs=2),
             _merge_block_function(cur.name, axis, rnd), cur, shape=cur.shape, dtype=work_dtype,
             chunks=cur.chunks, extra_projected_mem=2 * chunk_mem, fusable=False)
-    if pairs:
+    if pairs and not return_pairs:
         cur = blockwise(_arg_aggregate.program(nd, work_dtype), inds, cur, inds, dtype=np.int64)
     return cur
 
@@ -953,6 +996,109 @@ def searchsorted(x1: "Array", x2: "Array", right: bool = False) -> "Array":
             _search_block_function(x2.name, x1.name, b, None if counts is None else counts.name),
             *args, shape=x2.shape, dtype=np.int64, chunks=x2.chunks, extra_projected_mem=0, fusable=False)
     return counts
+
+
+# ------------------------------------------------------------------ run heads (unique_*)
+
+
+class _unique_block_function:
+    """Output block ``b`` reads chunk ``b`` of the sorted array and, after
+    block 0, chunk ``b - 1`` (for the predecessor of its first element)."""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __call__(self, out_key):
+        b = out_key[1]
+        return [(self.name, b)] if b == 0 else [(self.name, b), (self.name, b - 1)]
+
+
+def _unique_op(s, program, shape, dtype, chunks):
+    from ..lowering import unique_scratch_bytes
+    from .._native import UNIQUE_TILE
+
+    if s.ndim != 1 or s.size == 0:
+        raise ValueError("unique: a sorted 1-d array that is not empty")
+    # the chunk before is a second chunk of the one array argument; the tile
+    # counts are the launch's scratch
+    extra = s.chunkmem * 2 + unique_scratch_bytes(s.chunksize[0], UNIQUE_TILE)
+    return general_blockwise(program, _unique_block_function(s.name), s, shape=shape, dtype=dtype,
+                             chunks=chunks, extra_projected_mem=extra, fusable=False)
+
+
+def _unique_key_dtype(s, pairs):
+    dtype = np.dtype(s.dtype)
+    if pairs:
+        if dtype.names != ("v", "i"):
+            raise TypeError(f"unique: a pairs array has the fields v and i, not {dtype}")
+        dtype = dtype["v"]
+    return dtype
+
+
+def unique_count(s: "Array", pairs: bool = False) -> "Array":
+    """The int64 number of run heads of every chunk of the sorted 1-d array
+    ``s`` (plain keys, or with ``pairs`` the ``{v, i}`` array of
+    ``sort(.., return_pairs=True)``): shape ``(nb,)`` in chunks of 1, one never
+    fused ``ir.UniqueProgram`` op whose task ``b`` reads chunks ``b`` and
+    ``b - 1`` of ``s``."""
+    dtype = _unique_key_dtype(s, pairs)
+    nb = s.numblocks[0]
+    return _unique_op(s, ir.UniqueProgram(kind="count", pairs=bool(pairs), dtype=dtype, nargs=2),
+                      (nb,), np.int64, ((1,) * nb,))
+
+
+def unique_pack(s: "Array", pairs: bool = False, payload=None) -> "Array":
+    """The run heads of every chunk of the sorted 1-d array ``s`` packed at
+    the front of the chunk of the same number of an array of ``s``'s shape and
+    chunks, zeros behind them; the same two reads as ``unique_count``.
+    ``payload=None``: plain keys.  ``"position"``: ``{v, i}`` records, ``i`` the
+    position of the head in ``s``.  ``"index"`` (``pairs`` only): ``{v, i}``
+    records that keep the ``i`` of ``s``."""
+    dtype = _unique_key_dtype(s, pairs)
+    if payload not in (None, "position", "index") or (payload == "index" and not pairs):
+        raise ValueError(f"unique_pack: payload {payload!r}" + ("" if pairs else " of plain keys"))
+    out_dtype = dtype if payload is None else ir.sort_pairs_dtype(dtype)
+    return _unique_op(s, ir.UniqueProgram(kind="pack", pairs=bool(pairs), payload=payload, dtype=dtype, nargs=2),
+                      s.shape, out_dtype, s.chunks)
+
+
+def unique_gather(packed: "Array", counts_host, field=None) -> "Array":
+    """The first ``counts_host[b]`` elements of every chunk ``b`` of the 1-d
+    array ``packed``, concatenated: shape ``(k,)`` with ``k = sum(counts_host)
+    > 0`` in chunks of ``min(c, k)``, ``c`` the chunk length of ``packed``.
+    ``field`` reads one field of a structured ``packed``.
+
+    One op whatever the number of blocks: output block ``j`` copies the pieces
+    ``packed[b * c + lo : b * c + hi]`` that fall into its range, which the
+    host knows from the prefix sums of ``counts_host`` (``GatherRegions``,
+    lowered like ``concat``).  The pieces of a task are one output chunk's
+    worth of elements in all."""
+    counts = [int(v) for v in np.asarray(counts_host).reshape(-1)]
+    if packed.ndim != 1 or len(counts) != packed.numblocks[0]:
+        raise ValueError(f"unique_gather: {len(counts)} counts for {packed.numblocks} blocks")
+    if builtins.any(n < 0 or n > e for n, e in zip(counts, packed.chunks[0])):
+        raise ValueError("unique_gather: a count outside its chunk")
+    k = builtins.sum(counts)
+    if k == 0:
+        raise ValueError("unique_gather: nothing to gather")
+    dtype = np.dtype(packed.dtype) if field is None else np.dtype(packed.dtype)[field]
+    c = packed.chunksize[0]
+    chunks = normalize_chunks((builtins.min(c, k),), shape=(k,), dtype=dtype)
+    return map_direct(GatherRegions(chunks, packed.chunks[0], counts), packed, shape=(k,), dtype=dtype, chunks=chunks,
+                      extra_projected_mem=chunk_memory(dtype, to_chunksize(chunks)), field=field)
+
+
+def from_device(target: DeviceArray, spec=None) -> "Array":
+    """An array over a ``DeviceArray`` that an earlier compute has written:
+    a source without an op, so a plan that starts from it computes nothing
+    again.  The buffer stays alive as long as the arrays built on it, and the
+    executor counts it among the plan's HBM-resident arrays."""
+    if not isinstance(target, DeviceArray) or not target.written:
+        raise ValueError("from_device: a DeviceArray that has been computed")
+    if target.name is None:
+        target.name = gensym()
+    plan = Plan._new(target.name, "from_device", target)
+    return _Array()(target.name, target, spec or _default_spec(), plan)
 
 
 # ------------------------------------------------------------------ histograms

@@ -491,6 +491,30 @@ class HistogramProgram(Program):
     name: str = "histogram"
 
 
+@dataclass(frozen=True, eq=False)
+class UniqueProgram(Program):
+    """Per task (the unique_* set functions): the run heads of chunk ``b`` of
+    a sorted 1-d array, which is argument 0 -- plain ``dtype`` keys, or
+    ``sort_pairs_dtype(dtype)`` records with ``pairs``.  Element 0 of block 0
+    is a head; any other element is one iff its predecessor sorts strictly
+    before it (the order of ``SortProgram``: NaNs tie, -0.0 ties 0.0), and the
+    predecessor of a chunk's first element is the last element of chunk
+    ``b - 1``, the task's second chunk of the same array.
+
+    ``kind="count"``: the int64 number of heads of the chunk.  ``kind="pack"``:
+    the heads, packed at the front of an output chunk of the input chunk's
+    extent, zeros behind them.  ``payload=None`` packs plain keys; ``"position"``
+    packs ``{v, i}`` records with ``i`` the global position of the head in the
+    sorted array; ``"index"`` (pairs only) keeps the input record's ``i``.
+    Not an expression program: never fused, and the rewrites leave it alone."""
+    kind: str = "count"
+    pairs: bool = False
+    payload: Optional[str] = None
+    dtype: np.dtype = np.dtype("float64")
+    nargs: int = 1
+    name: str = "unique"
+
+
 def sort_pairs_dtype(dtype) -> np.dtype:
     """Element type of the arrays a pairs-mode sort works on."""
     return np.dtype([("v", np.dtype(dtype)), ("i", np.int64)])

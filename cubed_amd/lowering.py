@@ -657,6 +657,103 @@ class HistLaunch:
                                               self.path, self.work, stream), "cubed_hist_chunks")
 
 
+# ------------------------------------------------------------------ run heads
+
+UNIQUE_KINDS = {"count": nat.UNIQUE_COUNT, "pack": nat.UNIQUE_PACK}
+UNIQUE_PAYLOADS = {None: nat.UNIQUE_KEYS, "position": nat.UNIQUE_POSITION, "index": nat.UNIQUE_INDEX}
+
+
+def unique_scratch_bytes(n: int, tile: int) -> int:
+    """Scratch of one run-head task over ``n`` elements: an int64 per tile
+    and one for the total, rounded to 256 bytes."""
+    return -(-(-(-int(n) // tile) + 1) * 8 // 256) * 256
+
+
+def unique_task(src, prev, dst, offset: int, kind: str, payload: Optional[str]):
+    """One nat.UNIQUE_TASK_DTYPE row.  ``src``, ``prev`` and ``dst`` are (key
+    view, index view or None): the sorted chunk, the chunk before it (None
+    for block 0) and the output chunk -- a single int64 for ``kind="count"``,
+    a chunk of ``src``'s extent for ``"pack"``, with an index view iff there is
+    a ``payload``.  ``offset`` is the global position of the chunk's first
+    element.  The scratch address is filled in by UniqueLaunch."""
+    if kind not in UNIQUE_KINDS or payload not in UNIQUE_PAYLOADS or (kind == "count" and payload is not None):
+        raise LoweringError(f"unique: kind {kind!r} with payload {payload!r}")
+    for pair in (src, prev, dst):
+        for v in pair or ():
+            if v is not None and (len(v.extent) != 1 or list(v.stride) != [1]):
+                raise LoweringError("unique chunks must be 1-d and compact")
+    n = src[0].extent[0]
+    key = np.dtype(src[0].dtype)
+    for pair, what in ((src, "sorted"), (prev, "previous")):
+        if pair is None:
+            continue
+        if np.dtype(pair[0].dtype) != key:
+            raise LoweringError(f"unique of {key} keys after a {what} chunk of {pair[0].dtype}")
+        if pair[1] is not None and (np.dtype(pair[1].dtype) != np.int64 or pair[1].extent != pair[0].extent):
+            raise LoweringError(f"the index field of the {what} pairs chunk does not match its keys")
+    if prev is not None and prev[0].extent[0] < 1:
+        raise LoweringError("unique: an empty previous chunk")
+    if payload == "index" and src[1] is None:
+        raise LoweringError("unique: the index payload needs a pairs chunk")
+    if kind == "count":
+        if np.dtype(dst[0].dtype) != np.int64 or list(dst[0].extent) != [1] or dst[1] is not None:
+            raise LoweringError(f"unique counts into a {dst[0].dtype} chunk of extent {list(dst[0].extent)}")
+    else:
+        if np.dtype(dst[0].dtype) != key or list(dst[0].extent) != [n]:
+            raise LoweringError(f"unique packs {n} {key} keys into a {dst[0].dtype} chunk of extent "
+                                f"{list(dst[0].extent)}")
+        if (dst[1] is not None) != (payload is not None):
+            raise LoweringError(f"unique: payload {payload!r} and the output chunk's fields do not match")
+        if dst[1] is not None and (np.dtype(dst[1].dtype) != np.int64 or list(dst[1].extent) != [n]):
+            raise LoweringError("unique: the index field of the output chunk does not match its keys")
+    row = np.zeros((), dtype=nat.UNIQUE_TASK_DTYPE)
+    row["src_base"] = src[0].base
+    row["src_idx_base"] = src[1].base if src[1] is not None else 0
+    if prev is not None:
+        row["prev_base"], row["n_prev"] = prev[0].base, prev[0].extent[0]
+    row["dst_base"] = dst[0].base
+    row["dst_idx_base"] = dst[1].base if dst[1] is not None else 0
+    row["n"], row["offset"] = n, offset
+    return row
+
+
+class UniqueLaunch:
+    """One cubed_unique_chunks launch: a device table of run-head tasks (one
+    per chunk of the sorted array).  ``alloc(nbytes) -> address`` provides the
+    tile counts' scratch; ``sink``: the list of buffers the cache entry being
+    built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, ktype: int, kind: str, payload: Optional[str], device,
+                 sink=None, alloc=None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.ktype = ktype
+        self.kind, self.payload = kind, payload
+        self.scratch_bytes, self.work = 0, 0
+        if self.ntasks == 0:
+            return
+        tile = nat.unique_tile()
+        sizes = [unique_scratch_bytes(n, tile) for n in rows["n"].tolist()]
+        self.scratch_bytes = sum(sizes)
+        at = alloc(self.scratch_bytes)
+        for row, size in zip(rows, sizes):
+            row["scratch_base"] = at
+            at += size
+        self.work = nat.unique_work(rows, ktype, UNIQUE_KINDS[kind], UNIQUE_PAYLOADS[payload])
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0:
+            return
+        nat.check(nat.lib().cubed_unique_chunks(self.table.data_ptr(), self.ntasks, self.ktype,
+                                                UNIQUE_KINDS[self.kind], UNIQUE_PAYLOADS[self.payload],
+                                                self.work, stream), "cubed_unique_chunks")
+
+
 # ------------------------------------------------------------------ programs
 
 

@@ -398,7 +398,7 @@ class GpuDagExecutor(DagExecutor):
                     "(not expressible as a fused chunk program)")
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
                                     ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram,
-                                    ir.SearchProgram, ir.HistogramProgram)):
+                                    ir.SearchProgram, ir.HistogramProgram, ir.UniqueProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -451,6 +451,9 @@ class GpuDagExecutor(DagExecutor):
         if isinstance(program, ir.HistogramProgram):
             raise LoweringError("histogram runs on one GPU only: its counting launches are not "
                                 f"lowered for a world of {self.world} ranks")
+        if isinstance(program, ir.UniqueProgram):
+            raise LoweringError("the unique_* set functions run on one GPU only: their run-head launches "
+                                f"are not lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
                 not any(isinstance(l, ir.Concat) for l in ir.leaves_of_program(program)):
@@ -610,6 +613,8 @@ class GpuDagExecutor(DagExecutor):
             return [self._lower_search(program, cfg, target, keys)]
         if isinstance(program, ir.HistogramProgram):
             return [self._lower_hist(program, cfg, target, keys)]
+        if isinstance(program, ir.UniqueProgram):
+            return [self._lower_unique(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -864,6 +869,52 @@ class GpuDagExecutor(DagExecutor):
                 raise LoweringError("a histogram task reads the single chunk of its edges")
             rows[i] = hist_task(views[0], views[1], chunk_view(target, key), program.nbins)
         return HistLaunch(rows, ir.dtype_code(dtype), program.nbins, program.uniform, self.device, self._sink)
+
+    def _lower_unique(self, program, cfg, target, keys):
+        """One run-head task per output chunk (ir.UniqueProgram): task ``b``
+        reads chunk ``b`` of the sorted 1-d array and, after block 0, chunk
+        ``b - 1`` of the same array.  Pairs arrays are structured {v, i}, one
+        slab per field."""
+        from ...lowering import UniqueLaunch, sort_ktype, unique_task
+
+        ktype = sort_ktype(program.dtype)
+        in_dtype = ir.sort_pairs_dtype(program.dtype) if program.pairs else np.dtype(program.dtype)
+        if program.kind == "count":
+            out_dtype = np.dtype(np.int64)
+        else:
+            out_dtype = np.dtype(program.dtype) if program.payload is None else ir.sort_pairs_dtype(program.dtype)
+        if np.dtype(target.dtype) != out_dtype:
+            raise LoweringError(f"unique {program.kind} of {program.dtype} keys into a {target.dtype} array")
+        if target.ndim != 1:
+            raise LoweringError(f"unique {program.kind} into a {target.ndim}-d array")
+
+        def views(arr, coords, structured):
+            if structured:
+                return chunk_view(arr, coords, "v"), chunk_view(arr, coords, "i")
+            return chunk_view(arr, coords), None
+
+        rows = np.zeros(len(keys), dtype=nat.UNIQUE_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            b = key[0]
+            if len(args) != (1 if b == 0 else 2):
+                raise LoweringError(f"unique task {b} with {len(args)} inputs")
+            ins = []
+            for a, want in zip(args, (b, b - 1)):
+                if not isinstance(a, tuple):
+                    raise LoweringError("a unique task reads whole single chunks only")
+                if a[0] != args[0][0] or tuple(a[1:]) != (want,):
+                    raise LoweringError(f"unique task {b} reads chunk {tuple(a[1:])}, not its own chunk and the "
+                                        "one before it")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != in_dtype or src.ndim != 1:
+                    raise LoweringError(f"unique input {a[0]} is not a 1-d device array of {in_dtype}")
+                ins.append(views(src, a[1:], program.pairs))
+            src = self.device_source(cfg.reads_map[args[0][0]].array)
+            rows[i] = unique_task(ins[0], ins[1] if b else None,
+                                  views(target, key, program.kind == "pack" and program.payload is not None),
+                                  src.chunk_start((b,))[0], program.kind, program.payload)
+        return UniqueLaunch(rows, ktype, program.kind, program.payload, self.device, self._sink, self.scratch)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""

@@ -48,6 +48,9 @@
  *   cubed_hist_chunks    -> no reference interface: histogram is not in the
  *                           reference either; the semantics are numpy's
  *                           histogram of a chunk of values over given edges.
+ *   cubed_unique_chunks  -> no reference interface: the unique_* set functions
+ *                           are not in the reference either; the semantics are
+ *                           numpy's unique (equal_nan) of a sorted chunk.
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -575,6 +578,54 @@ int cubed_hist_path(const cubed_hist_task_t* tasks, int64_t ntasks, int32_t ktyp
  * Neither synchronises nor allocates. */
 int cubed_hist_chunks(const cubed_hist_task_t* d_tasks, int64_t ntasks, int32_t ktype, int64_t nbins,
                       int32_t path, int64_t work, void* stream);
+
+/* Run heads of a sorted chunk (the unique_* set functions; new symbols only,
+ * the ABI version is unchanged).  A task has a sorted 1-d run of n keys of the
+ * type ktype (one of the six sort key types), in the order of the sort:
+ * ascending, every NaN last and all NaNs tied, -0.0 tied with 0.0.  Element j
+ * is a head if it is the first element of the whole sorted array (j == 0 and
+ * prev_base == 0), else iff its predecessor sorts strictly before it; the
+ * predecessor of element 0 is element n_prev - 1 of the run at prev_base, the
+ * chunk before this one.
+ *   CUBED_UNIQUE_COUNT: dst_base gets the int64 number of heads.
+ *   CUBED_UNIQUE_PACK: dst_base, a run of n keys, gets the heads in order at
+ *     its front and zeros behind them.  With a payload dst_idx_base, a run of n
+ *     int64, gets next to every head offset + j (CUBED_UNIQUE_POSITION, its
+ *     global position in the sorted array) or element j of the int64 run at
+ *     src_idx_base (CUBED_UNIQUE_INDEX, the index field of a pairs chunk), and
+ *     zeros behind them.  The destination is never the source.
+ * scratch_base is the task's own ceil(n / CUBED_UNIQUE_TILE) + 1 int64.  No
+ * workgroup waits for another one and there are no atomics: results are
+ * bit-identical run to run. */
+#define CUBED_UNIQUE_TILE 4096   /* elements of one workgroup */
+#define CUBED_UNIQUE_COUNT 0     /* kinds */
+#define CUBED_UNIQUE_PACK 1
+#define CUBED_UNIQUE_KEYS 0      /* payloads: none, the packed elements are plain keys */
+#define CUBED_UNIQUE_POSITION 1
+#define CUBED_UNIQUE_INDEX 2
+
+typedef struct {
+  int64_t src_base, src_idx_base; /* device byte addresses; src_idx_base 0: plain keys */
+  int64_t prev_base;              /* the chunk before this one; 0: block 0 */
+  int64_t dst_base, dst_idx_base; /* dst_idx_base 0: no payload */
+  int64_t scratch_base;
+  int64_t n, n_prev;              /* elements of this chunk and of the one before */
+  int64_t offset;                 /* global position of element 0 in the sorted array */
+} cubed_unique_task_t;
+
+/* Host only: CUBED_UNIQUE_TILE of the loaded library. */
+int64_t cubed_unique_tile(void);
+/* Host only (no device call): validates a HOST copy of a task table and
+ * returns the workgroups per task of its launch, ceil(max n / tile); a
+ * negative CUBED_E_* code for a malformed table. */
+int64_t cubed_unique_work(const cubed_unique_task_t* tasks, int64_t ntasks, int32_t ktype, int32_t kind,
+                          int32_t payload);
+/* Over a DEVICE task table: one launch that counts the heads of every tile
+ * (ntasks x work workgroups), one that scans the tile counts of every task
+ * (ntasks workgroups) and, for CUBED_UNIQUE_PACK, one that packs (ntasks x
+ * work).  Neither synchronises nor allocates. */
+int cubed_unique_chunks(const cubed_unique_task_t* d_tasks, int64_t ntasks, int32_t ktype, int32_t kind,
+                        int32_t payload, int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
