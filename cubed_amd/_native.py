@@ -153,6 +153,14 @@ UNIQUE_TILE = 4096  # CUBED_UNIQUE_TILE: elements of one workgroup
 UNIQUE_COUNT, UNIQUE_PACK = 0, 1
 UNIQUE_KEYS, UNIQUE_POSITION, UNIQUE_INDEX = 0, 1, 2
 
+# cubed_select_task_t (one chunk whose selected elements are counted or packed)
+SELECT_TASK_DTYPE = np.dtype([
+    ("src_base", np.int64), ("val_base", np.int64), ("dst_base", np.int64), ("scratch_base", np.int64),
+    ("n", np.int64), ("offset", np.int64),
+])
+SELECT_TILE_BYTES = 16384  # CUBED_SELECT_TILE_BYTES: bytes of the run one workgroup owns
+SELECT_COUNT, SELECT_PACK = 0, 1
+
 
 class NativeError(RuntimeError):
     pass
@@ -215,6 +223,12 @@ def lib():
     L.cubed_unique_work.restype = c_int64
     L.cubed_unique_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p]
     L.cubed_unique_chunks.restype = c_int
+    L.cubed_select_tile_bytes.argtypes = []
+    L.cubed_select_tile_bytes.restype = c_int64
+    L.cubed_select_work.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32]
+    L.cubed_select_work.restype = c_int64
+    L.cubed_select_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_select_chunks.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -320,6 +334,7 @@ EXPORTED_SYMBOLS = (
     "cubed_search_tile", "cubed_search_path", "cubed_search_chunks",
     "cubed_hist_bins_lds", "cubed_hist_path", "cubed_hist_chunks",
     "cubed_unique_tile", "cubed_unique_work", "cubed_unique_chunks",
+    "cubed_select_tile_bytes", "cubed_select_work", "cubed_select_chunks",
 )
 
 
@@ -390,6 +405,21 @@ def unique_work(rows: np.ndarray, ktype: int, kind: int, payload: int) -> int:
     work = int(lib().cubed_unique_work(rows.ctypes.data, len(rows), ktype, kind, payload))
     if work < 0:
         check(work, "cubed_unique_work")
+    return work
+
+
+def select_tile_bytes() -> int:
+    """Bytes of a chunk one workgroup of the select kernels owns (host only)."""
+    return int(lib().cubed_select_tile_bytes())
+
+
+def select_work(rows: np.ndarray, esize: int, ignore_sign: bool, kind: int, vsize: int) -> int:
+    """Validates a host table of SELECT_TASK_DTYPE rows and gives the
+    workgroups per task of its launch (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=SELECT_TASK_DTYPE)
+    work = int(lib().cubed_select_work(rows.ctypes.data, len(rows), esize, int(ignore_sign), kind, vsize))
+    if work < 0:
+        check(work, "cubed_select_work")
     return work
 
 

@@ -54,7 +54,7 @@ from .manipulation_functions import (
     squeeze,
     stack,
 )
-from .searching_functions import argmax, argmin, searchsorted, where
+from .searching_functions import argmax, argmin, count_nonzero, nonzero, searchsorted, where
 from .set_functions import unique_all, unique_counts, unique_inverse, unique_values
 from .sorting_functions import argsort, sort
 from .statistical_functions import cumulative_sum, histogram, max, mean, min, prod, std, sum, var

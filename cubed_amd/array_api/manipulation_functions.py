@@ -177,6 +177,21 @@ def flatten(x):
     return reshape(x, (-1,))
 
 
+def _ravel(x):
+    """``x`` flattened in C order.  An N-d ``x`` is first rechunked to whole
+    rows -- as many of them as hold about the elements of one chunk of ``x``,
+    one at the least -- so that every chunk is one run of the flat array."""
+    import math
+
+    from ..core.ops import rechunk
+
+    if x.ndim > 1:
+        row = math.prod(x.shape[1:])
+        rows = max(1, min(x.shape[0], math.prod(x.chunksize) // row))
+        x = rechunk(x, (rows,) + tuple(x.shape[1:]))
+    return flatten(x)
+
+
 def reshape(x, /, shape, *, copy=None):
     """array_api/manipulation_functions.py:210-246 (dask's reshape): rechunk
     so every input block maps to one output block, then reinterpret each

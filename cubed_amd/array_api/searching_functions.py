@@ -16,6 +16,60 @@ def where(condition, x1, x2, /):
     return elemwise("where", condition, x1, x2, dtype=dtype)
 
 
+def nonzero(x, /):
+    """The indices of the elements of ``x`` that are not zero: a tuple of
+    ``x.ndim`` int64 1-d arrays, in C order -- ``np.nonzero(x)``.  bool, every
+    integer width, float32, float64 and bfloat16; -0.0 is zero, NaNs of either
+    sign, infinities and denormals are not.  A 0-d ``x`` raises ValueError and a
+    complex one TypeError.
+
+    The reference has no nonzero, so parity is unpinned; numpy is the
+    yardstick.  The shape of the result depends on the data, so the function is
+    EAGER like ``unique_values``: while the call executes it counts the
+    selected elements of every chunk of the flattened ``x`` and packs their
+    flat positions (``core.ops.select_count`` / ``select_pack``) on
+    ``x.spec.executor`` and reads the counts to the host.  The arrays returned
+    are lazy and start from the packed positions in HBM; for ``ndim > 1`` they
+    are ``(pos // stride_d) % shape_d`` of the flat positions.  One GPU.  To
+    only count, use ``count_nonzero``, which is lazy."""
+    import math
+
+    from ..core.ops import select_nonzero
+    from .creation_functions import empty
+    from .dtypes import _real_numeric_dtypes, bool as _bool, int64
+    from .manipulation_functions import _ravel
+
+    if x.dtype not in _real_numeric_dtypes and x.dtype != _bool:
+        raise TypeError("Only boolean and real numeric dtypes are allowed in nonzero")
+    if x.ndim == 0:
+        raise ValueError("nonzero is not supported for zero-dimensional arrays; use "
+                         "nonzero(reshape(x, (1,))) instead")
+    pos = select_nonzero(_ravel(x)) if x.size else None
+    if pos is None:
+        return tuple(empty((0,), dtype=int64, chunks=(1,), spec=x.spec) for _ in range(x.ndim))
+    if x.ndim == 1:
+        return (pos,)
+    out = []
+    for d in range(x.ndim):
+        stride = math.prod(x.shape[d + 1:])
+        idx = pos if d == x.ndim - 1 else pos // stride
+        out.append(idx if d == 0 else idx % int(x.shape[d]))
+    return tuple(out)
+
+
+def count_nonzero(x, /, *, axis=None, keepdims=False):
+    """The int64 number of elements of ``x`` that are not zero, over ``axis``
+    (an int, a tuple of ints or None for all) -- ``np.count_nonzero`` (Array
+    API 2024.12).  Lazy and of a shape that does not depend on the data: the
+    ``sum`` of ``astype(x != 0, int64)``; nothing runs on the select kernel."""
+    from .data_type_functions import astype
+    from .dtypes import bool as _bool, int64
+    from .statistical_functions import sum as _sum
+
+    flags = x if x.dtype == _bool else x != 0
+    return _sum(astype(flags, int64), axis=axis, dtype=int64, keepdims=keepdims)
+
+
 def searchsorted(x1, x2, /, *, side="left", sorter=None):
     """For every element ``v`` of ``x2`` (any shape) the index at which it
     would be inserted into the sorted 1-d ``x1`` to keep it sorted: the number

@@ -16,30 +16,16 @@ as ``index()`` does for an array index, and read the per-chunk counts to the
 host.  What they return is lazy again: it starts from the packed arrays that
 are already in HBM (``core.ops.from_device``) and never sorts a second time."""
 
-import math
 from collections import namedtuple
 
 import numpy as np
 
 from .dtypes import int64
+from .manipulation_functions import _ravel  # noqa: F401  (shared with nonzero and x[mask])
 
 UniqueAllResult = namedtuple("UniqueAllResult", ["values", "indices", "inverse_indices", "counts"])
 UniqueCountsResult = namedtuple("UniqueCountsResult", ["values", "counts"])
 UniqueInverseResult = namedtuple("UniqueInverseResult", ["values", "inverse_indices"])
-
-
-def _ravel(x):
-    """``x`` flattened in C order.  An N-d ``x`` is first rechunked to whole
-    rows -- as many of them as hold about the elements of one chunk of ``x``,
-    one at the least -- so that every chunk is one run of the flat array."""
-    from ..core.ops import rechunk
-    from .manipulation_functions import flatten
-
-    if x.ndim > 1:
-        row = math.prod(x.shape[1:])
-        rows = max(1, min(x.shape[0], math.prod(x.chunksize) // row))
-        x = rechunk(x, (rows,) + tuple(x.shape[1:]))
-    return flatten(x)
 
 
 def _unique(x, what, index=False, inverse=False, counts=False):

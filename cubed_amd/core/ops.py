@@ -299,9 +299,17 @@ def _is_int(x):
 
 def index(x, key):
     """Subset an array along one or more axes (basic indexing: slices with
-    step >= 1, integers, None, Ellipsis, and one integer list)."""
+    step >= 1, integers, None, Ellipsis, and one integer list), or select
+    the elements under a boolean mask of ``x``'s shape (the sole index; eager,
+    see ``_index_mask``)."""
+    if _is_bool_key(key):
+        return _index_mask(x, key)
     if not isinstance(key, tuple):
         key = (key,)
+    if any(_is_bool_key(ind) for ind in key):
+        # never read a boolean array as integer indices
+        raise NotImplementedError("a boolean array index next to other indices is not supported: "
+                                  "a boolean mask must be the sole index and have the array's shape")
     if all(isinstance(ind, slice) and ind == slice(None) for ind in key):
         return x
     where_none = [i for i, ind in enumerate(key) if ind is None]
@@ -1086,6 +1094,114 @@ def unique_gather(packed: "Array", counts_host, field=None) -> "Array":
     chunks = normalize_chunks((builtins.min(c, k),), shape=(k,), dtype=dtype)
     return map_direct(GatherRegions(chunks, packed.chunks[0], counts), packed, shape=(k,), dtype=dtype, chunks=chunks,
                       extra_projected_mem=chunk_memory(dtype, to_chunksize(chunks)), field=field)
+
+
+# ------------------------------------------------------------------ selection (nonzero, x[mask])
+
+
+class _select_block_function:
+    """Output block ``b`` reads chunk ``b`` of every argument."""
+
+    def __init__(self, names):
+        self.names = tuple(names)
+
+    def __call__(self, out_key):
+        return [(name, out_key[1]) for name in self.names]
+
+
+def _select_op(f, values, program, shape, dtype, chunks):
+    from ..lowering import select_predicate, select_scratch_bytes
+    from .._native import SELECT_TILE_BYTES
+
+    if f.ndim != 1 or f.size == 0:
+        raise ValueError("select: a 1-d array that is not empty")
+    try:
+        esize, _ = select_predicate(f.dtype)
+    except Exception as e:
+        raise TypeError(str(e)) from None
+    args = (f,) if values is None else (f, values)
+    # the input and output chunks are counted by general_blockwise; the tile counts are the launch's scratch
+    extra = select_scratch_bytes(f.chunksize[0], esize, SELECT_TILE_BYTES)
+    return general_blockwise(program, _select_block_function(a.name for a in args), *args, shape=shape,
+                             dtype=dtype, chunks=chunks, extra_projected_mem=extra, fusable=False)
+
+
+def select_count(f: "Array") -> "Array":
+    """The int64 number of elements of every chunk of the 1-d array ``f`` that
+    are not zero (bool, integers, float32, float64, bfloat16; -0.0 is zero, a
+    NaN is not): shape ``(nb,)`` in chunks of 1, one never fused
+    ``ir.SelectProgram`` op whose task ``b`` reads chunk ``b`` only."""
+    nb = f.numblocks[0]
+    return _select_op(f, None, ir.SelectProgram(kind="count", dtype=np.dtype(f.dtype), nargs=1),
+                      (nb,), np.int64, ((1,) * nb,))
+
+
+def select_pack(f: "Array", values=None) -> "Array":
+    """An array of ``f``'s shape and chunks that holds, packed at the front of
+    every chunk with zeros behind them, the global flat positions of the
+    chunk's elements of ``f`` that are not zero (int64, ``values=None``), or
+    the elements of ``values`` at those places (``values.dtype``; ``values`` is
+    1-d with ``f``'s shape and chunks, and task ``b`` reads chunk ``b`` of
+    both).  One never fused ``ir.SelectProgram`` op."""
+    if values is None:
+        return _select_op(f, None, ir.SelectProgram(kind="pack", dtype=np.dtype(f.dtype), nargs=1),
+                          f.shape, np.int64, f.chunks)
+    vdtype = np.dtype(values.dtype)
+    if vdtype.names or vdtype.kind == "c" or vdtype.itemsize not in (1, 2, 4, 8):
+        raise TypeError(f"select_pack: values of {vdtype}")
+    if values.shape != f.shape or values.chunks != f.chunks:
+        raise ValueError(f"select_pack: values of shape {values.shape} in chunks {values.chunks} for a mask of "
+                         f"shape {f.shape} in chunks {f.chunks}")
+    return _select_op(f, values, ir.SelectProgram(kind="pack", payload="values", dtype=np.dtype(f.dtype),
+                                                  value_dtype=vdtype, nargs=2),
+                      f.shape, vdtype, f.chunks)
+
+
+def select_nonzero(f: "Array", values=None):
+    """EAGER: runs ``select_count(f)`` and one ``select_pack(f, values)`` on
+    ``f.spec.executor`` now and reads the per-chunk counts to the host.
+    Returns the lazy 1-d array of the ``k`` packed elements, gathered from HBM
+    (``unique_gather`` over ``from_device``), or None if ``k == 0``."""
+    counts = select_count(f)
+    packed = select_pack(f, values)
+    compute(counts, packed, _return_in_memory_array=False)
+    per_chunk = counts._read_stored()
+    if int(per_chunk.sum()) == 0:
+        return None
+    return unique_gather(from_device(packed.zarray, f.spec), per_chunk)
+
+
+def _is_bool_key(ind):
+    return isinstance(ind, (CoreArray, np.ndarray)) and np.dtype(ind.dtype) == np.bool_
+
+
+def _index_mask(x, mask):
+    """``x[mask]`` for a bool ``mask`` of ``x``'s shape: the selected elements
+    in C order, 1-d.  EAGER, like ``select_nonzero``."""
+    from ..array_api.creation_functions import empty
+    from ..array_api.manipulation_functions import _ravel
+
+    if np.dtype(x.dtype).kind == "c":
+        raise TypeError("boolean-mask indexing of a complex array is not supported")
+    if tuple(mask.shape) != tuple(x.shape):
+        if mask.ndim < x.ndim:
+            raise NotImplementedError(
+                f"a boolean mask of fewer dimensions ({mask.ndim}) than the array ({x.ndim}) is not supported: "
+                "the mask must have the array's shape")
+        raise IndexError(f"boolean index of shape {tuple(mask.shape)} did not match the indexed array of "
+                         f"shape {tuple(x.shape)}")
+    if x.ndim == 0:
+        raise NotImplementedError("boolean-mask indexing of a 0-d array is not supported")
+    if isinstance(mask, np.ndarray):
+        mask = from_array(mask, chunks=x.chunks, spec=x.spec)
+    elif mask.chunks != x.chunks:
+        mask = rechunk(mask, x.chunksize)
+    out = None
+    if x.size:
+        out = select_nonzero(_ravel(mask), _ravel(x))
+    if out is None:
+        out = empty((0,), dtype=x.dtype, chunks=(1,), spec=x.spec)
+    return out
 
 
 def from_device(target: DeviceArray, spec=None) -> "Array":

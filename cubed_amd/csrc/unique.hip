@@ -17,9 +17,9 @@
 //   k_unique_count  a tile's heads: popcounts of the ballots, the four waves'
 //                   sums through LDS, one int64 per tile into the task's scratch.
 //   k_unique_scan   one workgroup per task: the exclusive prefix of the tile
-//                   counts in place (wave scan with __shfl_up, wave totals
-//                   through LDS, a running carry), the total behind them and,
-//                   for CUBED_UNIQUE_COUNT, into dst.
+//                   counts in place (scan_tile_counts of tile_scan.h, shared
+//                   with select.hip), the total behind them and, for
+//                   CUBED_UNIQUE_COUNT, into dst.
 //   k_unique_pack   the flags again, from keys kept in registers; a head goes to
 //                   dst[tile offset + heads of the earlier waves + heads of the
 //                   earlier rounds + popcount(ballot below the lane)], so the
@@ -33,6 +33,7 @@
 #include <stdio.h>
 #include "common.h"
 #include "sort_keys.h"
+#include "tile_scan.h"
 
 namespace cubed {
 extern thread_local char g_err[512];
@@ -106,39 +107,11 @@ __global__ __launch_bounds__(kBlock) void k_unique_count(const cubed_unique_task
 // Grid: one workgroup per task.
 __global__ __launch_bounds__(kBlock) void k_unique_scan(const cubed_unique_task_t* __restrict__ tasks,
                                                         int64_t ntasks, int32_t write_count) {
-  __shared__ int64_t wtot[kWaves];
   const int64_t ti = blockIdx.x;
   if (ti >= ntasks) return;
   const cubed_unique_task_t* __restrict__ K = tasks + ti;
-  const int64_t ntiles = (K->n + kTile - 1) / kTile;
-  CUBED_G int64_t* __restrict__ sc = (CUBED_G int64_t*)(uintptr_t)K->scratch_base;
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  int64_t carry = 0;  // the same in every thread
-  for (int64_t base = 0; base < ntiles; base += kBlock) {
-    const int64_t i = base + tid;
-    const int64_t c = i < ntiles ? sc[i] : 0;
-    int64_t s = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t up = __shfl_up(s, d);
-      if (lane >= d) s += up;
-    }
-    if (lane == 63) wtot[w] = s;
-    __syncthreads();
-    int64_t before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-      if (k < w) before += wtot[k];
-      total += wtot[k];
-    }
-    if (i < ntiles) sc[i] = carry + before + s - c;
-    carry += total;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    sc[ntiles] = carry;
-    if (write_count) *(CUBED_G int64_t*)(uintptr_t)K->dst_base = carry;
-  }
+  scan_tile_counts((CUBED_G int64_t*)(uintptr_t)K->scratch_base, (K->n + kTile - 1) / kTile,
+                   write_count ? (CUBED_G int64_t*)(uintptr_t)K->dst_base : nullptr);
 }
 
 // Grid: as k_unique_count.  PAYLOAD: CUBED_UNIQUE_KEYS, _POSITION or _INDEX.

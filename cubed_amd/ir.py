@@ -515,6 +515,26 @@ class UniqueProgram(Program):
     name: str = "unique"
 
 
+@dataclass(frozen=True, eq=False)
+class SelectProgram(Program):
+    """Per task (nonzero, ``x[mask]``): the elements of chunk ``b`` of a 1-d
+    array of ``dtype``, argument 0, that are not zero -- bool, any integer,
+    float32, float64 or bfloat16; -0.0 is zero, NaNs are not.
+
+    ``kind="count"``: the int64 number of them.  ``kind="pack"``: packed at the
+    front of an output chunk of the input chunk's extent, zeros behind them,
+    ``payload=None`` their int64 positions in the whole array, ``"values"`` the
+    elements at their places in chunk ``b`` of argument 1, an array of
+    ``value_dtype`` (any real dtype) with the shape and chunks of argument 0.
+    Not an expression program: never fused, and the rewrites leave it alone."""
+    kind: str = "count"
+    payload: Optional[str] = None
+    dtype: np.dtype = np.dtype("bool")
+    value_dtype: Optional[np.dtype] = None
+    nargs: int = 1
+    name: str = "select"
+
+
 def sort_pairs_dtype(dtype) -> np.dtype:
     """Element type of the arrays a pairs-mode sort works on."""
     return np.dtype([("v", np.dtype(dtype)), ("i", np.int64)])

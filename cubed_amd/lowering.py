@@ -754,6 +754,99 @@ class UniqueLaunch:
                                                 self.work, stream), "cubed_unique_chunks")
 
 
+# ------------------------------------------------------------------ selection (nonzero, x[mask])
+
+SELECT_KINDS = {"count": nat.SELECT_COUNT, "pack": nat.SELECT_PACK}
+SELECT_PAYLOADS = (None, "values")
+
+
+def select_scratch_bytes(n: int, esize: int, tile_bytes: int) -> int:
+    """Scratch of one select task over ``n`` elements of ``esize`` bytes: an
+    int64 per tile and one for the total, rounded to 256 bytes."""
+    return -(-(-(-int(n) * esize // tile_bytes) + 1) * 8 // 256) * 256
+
+
+def select_predicate(dtype):
+    """(element size, ignore_sign) of the nonzero test on ``dtype``: an element
+    is selected iff its bits, for a float without the sign bit, are not 0."""
+    dtype = np.dtype(dtype)
+    if dtype.names or not (dtype.kind in "biuf" or ir.is_bf16(dtype)) or dtype.itemsize not in (1, 2, 4, 8):
+        raise LoweringError(f"select on {dtype} elements is not lowered")
+    return dtype.itemsize, ir.is_float(dtype)
+
+
+def select_task(src, val, dst, offset: int, kind: str, payload: Optional[str]):
+    """One nat.SELECT_TASK_DTYPE row.  ``src`` is the chunk the predicate
+    reads, ``val`` the chunk of the values (``payload="values"``) or None, and
+    ``dst`` the output chunk: a single int64 for ``kind="count"``, for
+    ``"pack"`` a chunk of ``src``'s extent, int64 or of ``val``'s dtype.
+    ``offset`` is the global position of the chunk's first element.  The
+    scratch address is filled in by SelectLaunch."""
+    if kind not in SELECT_KINDS or payload not in SELECT_PAYLOADS or (kind == "count" and payload is not None):
+        raise LoweringError(f"select: kind {kind!r} with payload {payload!r}")
+    if (val is not None) != (payload == "values"):
+        raise LoweringError(f"select: payload {payload!r} and the task's value chunk do not match")
+    for v in (src, val, dst):
+        if v is not None and (len(v.extent) != 1 or list(v.stride) != [1]):
+            raise LoweringError("select chunks must be 1-d and compact")
+    n = src.extent[0]
+    if val is not None and list(val.extent) != [n]:
+        raise LoweringError(f"select: {val.extent[0]} values for {n} elements")
+    if kind == "count":
+        if np.dtype(dst.dtype) != np.int64 or list(dst.extent) != [1]:
+            raise LoweringError(f"select counts into a {dst.dtype} chunk of extent {list(dst.extent)}")
+    else:
+        want = np.dtype(np.int64) if val is None else np.dtype(val.dtype)
+        if np.dtype(dst.dtype) != want or list(dst.extent) != [n]:
+            raise LoweringError(f"select packs {n} {want} elements into a {dst.dtype} chunk of extent "
+                                f"{list(dst.extent)}")
+    row = np.zeros((), dtype=nat.SELECT_TASK_DTYPE)
+    row["src_base"] = src.base
+    row["val_base"] = val.base if val is not None else 0
+    row["dst_base"] = dst.base
+    row["n"], row["offset"] = n, offset
+    return row
+
+
+class SelectLaunch:
+    """One cubed_select_chunks launch: a device table of select tasks (one
+    per chunk of the flat array).  ``esize`` and ``ignore_sign`` are the
+    predicate's (select_predicate), ``vsize`` the element size of the packed
+    values, 0 for positions and counts.  ``alloc(nbytes) -> address`` provides
+    the tile counts' scratch; ``sink``: the list of buffers the cache entry
+    being built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, esize: int, ignore_sign: bool, kind: str, vsize: int, device,
+                 sink=None, alloc=None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.esize, self.ignore_sign = esize, bool(ignore_sign)
+        self.kind, self.vsize = kind, vsize
+        self.scratch_bytes, self.work = 0, 0
+        if self.ntasks == 0:
+            return
+        tile_bytes = nat.select_tile_bytes()
+        sizes = [select_scratch_bytes(n, esize, tile_bytes) for n in rows["n"].tolist()]
+        self.scratch_bytes = sum(sizes)
+        at = alloc(self.scratch_bytes)
+        for row, size in zip(rows, sizes):
+            row["scratch_base"] = at
+            at += size
+        self.work = nat.select_work(rows, esize, self.ignore_sign, SELECT_KINDS[kind], vsize)
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0:
+            return
+        nat.check(nat.lib().cubed_select_chunks(self.table.data_ptr(), self.ntasks, self.esize,
+                                                int(self.ignore_sign), SELECT_KINDS[self.kind], self.vsize,
+                                                self.work, stream), "cubed_select_chunks")
+
+
 # ------------------------------------------------------------------ programs
 
 

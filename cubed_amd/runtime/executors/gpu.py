@@ -398,7 +398,8 @@ class GpuDagExecutor(DagExecutor):
                     "(not expressible as a fused chunk program)")
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
                                     ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram,
-                                    ir.SearchProgram, ir.HistogramProgram, ir.UniqueProgram)):
+                                    ir.SearchProgram, ir.HistogramProgram, ir.UniqueProgram,
+                                    ir.SelectProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -453,6 +454,9 @@ class GpuDagExecutor(DagExecutor):
                                 f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.UniqueProgram):
             raise LoweringError("the unique_* set functions run on one GPU only: their run-head launches "
+                                f"are not lowered for a world of {self.world} ranks")
+        if isinstance(program, ir.SelectProgram):
+            raise LoweringError("nonzero and boolean-mask indexing run on one GPU only: their select launches "
                                 f"are not lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
@@ -615,6 +619,8 @@ class GpuDagExecutor(DagExecutor):
             return [self._lower_hist(program, cfg, target, keys)]
         if isinstance(program, ir.UniqueProgram):
             return [self._lower_unique(program, cfg, target, keys)]
+        if isinstance(program, ir.SelectProgram):
+            return [self._lower_select(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -915,6 +921,48 @@ class GpuDagExecutor(DagExecutor):
                                   views(target, key, program.kind == "pack" and program.payload is not None),
                                   src.chunk_start((b,))[0], program.kind, program.payload)
         return UniqueLaunch(rows, ktype, program.kind, program.payload, self.device, self._sink, self.scratch)
+
+    def _lower_select(self, program, cfg, target, keys):
+        """One select task per output chunk (ir.SelectProgram): task ``b`` reads
+        chunk ``b`` of the 1-d array the predicate looks at and, with the
+        ``"values"`` payload, chunk ``b`` of the values."""
+        from ...lowering import SelectLaunch, select_predicate, select_task
+
+        esize, ignore_sign = select_predicate(program.dtype)
+        values = program.payload == "values"
+        if program.kind == "count":
+            out_dtype = np.dtype(np.int64)
+        else:
+            out_dtype = np.dtype(program.value_dtype) if values else np.dtype(np.int64)
+        vsize = out_dtype.itemsize if values else 0
+        if values and (out_dtype.names or out_dtype.kind == "c" or vsize not in (1, 2, 4, 8)):
+            raise LoweringError(f"select of {out_dtype} values is not lowered")
+        if np.dtype(target.dtype) != out_dtype:
+            raise LoweringError(f"select {program.kind} into a {target.dtype} array, not {out_dtype}")
+        if target.ndim != 1:
+            raise LoweringError(f"select {program.kind} into a {target.ndim}-d array")
+        in_dtypes = [np.dtype(program.dtype)] + ([out_dtype] if values else [])
+        rows = np.zeros(len(keys), dtype=nat.SELECT_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            b = key[0]
+            if len(args) != len(in_dtypes):
+                raise LoweringError(f"select task {b} with {len(args)} inputs")
+            ins = []
+            for a, dt in zip(args, in_dtypes):
+                if not isinstance(a, tuple):
+                    raise LoweringError("a select task reads whole single chunks only")
+                if tuple(a[1:]) != (b,):
+                    raise LoweringError(f"select task {b} reads chunk {tuple(a[1:])}, not its own chunk")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != dt or src.ndim != 1:
+                    raise LoweringError(f"select input {a[0]} is not a 1-d device array of {dt}")
+                ins.append((src, chunk_view(src, a[1:])))
+            if values and ins[1][0].chunks != ins[0][0].chunks:
+                raise LoweringError("select: the values and the mask are chunked differently")
+            rows[i] = select_task(ins[0][1], ins[1][1] if values else None, chunk_view(target, key),
+                                  ins[0][0].chunk_start((b,))[0], program.kind, program.payload)
+        return SelectLaunch(rows, esize, ignore_sign, program.kind, vsize, self.device, self._sink, self.scratch)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""

@@ -51,6 +51,9 @@
  *   cubed_unique_chunks  -> no reference interface: the unique_* set functions
  *                           are not in the reference either; the semantics are
  *                           numpy's unique (equal_nan) of a sorted chunk.
+ *   cubed_select_chunks  -> no reference interface: nonzero and boolean-mask
+ *                           indexing are not in the reference either; the
+ *                           semantics are numpy's flatnonzero and a[mask].
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -626,6 +629,52 @@ int64_t cubed_unique_work(const cubed_unique_task_t* tasks, int64_t ntasks, int3
  * work).  Neither synchronises nor allocates. */
 int cubed_unique_chunks(const cubed_unique_task_t* d_tasks, int64_t ntasks, int32_t ktype, int32_t kind,
                         int32_t payload, int64_t work, void* stream);
+
+/* Selection by a one-element predicate (nonzero, x[mask]; new symbols only,
+ * the ABI version is unchanged).  A task has a 1-d run of n elements of esize
+ * bytes (1, 2, 4 or 8) at src_base.  Element j is selected iff
+ * (bits & m) != 0, where m is all ones, or with ignore_sign all ones but the
+ * top bit of the element: -0.0 is not selected, NaNs, infinities, denormals
+ * and the most negative integer are.
+ *   CUBED_SELECT_COUNT: dst_base gets the int64 number of selected elements;
+ *     vsize and every val_base are 0.
+ *   CUBED_SELECT_PACK, vsize 0: dst_base, a run of n int64, gets offset + j of
+ *     every selected element in order at its front and zeros behind them;
+ *     every val_base is 0.
+ *   CUBED_SELECT_PACK, vsize 1, 2, 4 or 8: dst_base, a run of n elements of
+ *     vsize bytes, gets element j of the run at val_base for every selected j
+ *     in order at its front and zeros behind them.
+ * src_base is a multiple of 16 and the storage behind the run extends to the
+ * next multiple of 16 bytes: the kernels load whole 16-byte vectors, never one
+ * that starts at or past element n, and mask off the elements at or past n.
+ * The destination is never the source or the values.  scratch_base is the
+ * task's own ceil(n * esize / tile bytes) + 1 int64.  No workgroup waits for
+ * another one and there are no atomics: results are bit-identical run to
+ * run. */
+#define CUBED_SELECT_TILE_BYTES 16384 /* bytes of src one workgroup owns */
+#define CUBED_SELECT_COUNT 0          /* kinds */
+#define CUBED_SELECT_PACK 1
+
+typedef struct {
+  int64_t src_base;      /* the run the predicate reads: n elements of esize bytes */
+  int64_t val_base;      /* 0: pack positions; else n elements of vsize bytes to pack */
+  int64_t dst_base, scratch_base;
+  int64_t n, offset;     /* offset: global flat position of element 0 */
+} cubed_select_task_t;
+
+/* Host only: CUBED_SELECT_TILE_BYTES of the loaded library. */
+int64_t cubed_select_tile_bytes(void);
+/* Host only (no device call): validates a HOST copy of a task table and
+ * returns the workgroups per task of its launch, ceil(max n * esize / tile
+ * bytes); a negative CUBED_E_* code for a malformed table. */
+int64_t cubed_select_work(const cubed_select_task_t* tasks, int64_t ntasks, int32_t esize,
+                          int32_t ignore_sign, int32_t kind, int32_t vsize);
+/* Over a DEVICE task table: one launch that counts the selected elements of
+ * every tile (ntasks x work workgroups), one that scans the tile counts of
+ * every task (ntasks workgroups) and, for CUBED_SELECT_PACK, one that packs
+ * (ntasks x work).  Neither synchronises nor allocates. */
+int cubed_select_chunks(const cubed_select_task_t* d_tasks, int64_t ntasks, int32_t esize,
+                        int32_t ignore_sign, int32_t kind, int32_t vsize, int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
