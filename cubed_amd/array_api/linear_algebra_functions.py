@@ -72,7 +72,7 @@ def outer(x1, x2, /):
 
 
 def tensordot(x1, x2, /, *, axes=2):
-    from .statistical_functions import sum
+    from .statistical_functions import _np_sum
 
     if x1.dtype not in _numeric_dtypes or x2.dtype not in _numeric_dtypes:
         raise TypeError("Only numeric dtypes are allowed in tensordot")
@@ -97,7 +97,12 @@ def tensordot(x1, x2, /, *, axes=2):
         adjust_chunks[x1_ind[a1]] = lambda c: 1
     out = blockwise(ir.TensordotProgram(axes=(x1_axes, x2_axes), out_dtype=np.dtype(dtype)),
                     out_ind, x1, x1_ind, x2, x2_ind, dtype=dtype, adjust_chunks=adjust_chunks)
-    return sum(out, axis=x1_axes, dtype=dtype)
+    # Not xp.sum: the chunk products are summed in their own dtype, as matmul's
+    # k-sum is (_sum_wo_cat) -- the plan the GEMM chain fusion recognises
+    # (gemm_chains._is_ksum wants the sum's field in the products' dtype), and
+    # the float32 association its tests state.  xp.sum would keep float64
+    # partials for a float32 result.
+    return reduction(out, _np_sum, axis=x1_axes, dtype=dtype, extra_func_kwargs=dict(dtype=dtype))
 
 
 def vecdot(x1, x2, /, *, axis=-1):

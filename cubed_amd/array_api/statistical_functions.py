@@ -67,13 +67,24 @@ def _default_sum_dtype(dt):
     return dt
 
 
+def _partials_dtype(dtype):
+    """The dtype a sum / prod keeps between its rounds.  The kernels
+    accumulate floats in float64 whatever the result dtype; a float32 or
+    bfloat16 result keeps its per-chunk partials in float64 too and is
+    rounded once, by the final astype -- partials stored in the result dtype
+    would add one rounding per partial and combine round (a float32 sum over
+    (7, 13) in (3, 5) chunks was off by two spacings)."""
+    return float64 if np.dtype(dtype) in (float32, bfloat16) else dtype
+
+
 def prod(x, /, *, axis=None, dtype=None, keepdims=False):
     if x.dtype not in _numeric_dtypes:
         raise TypeError("Only numeric dtypes are allowed in prod")
     if dtype is None:
         dtype = _default_sum_dtype(x.dtype)
-    return reduction(x, _np_prod, axis=axis, dtype=dtype, keepdims=keepdims,
-                     extra_func_kwargs=dict(dtype=dtype))
+    partials = _partials_dtype(dtype)
+    return reduction(x, _np_prod, axis=axis, intermediate_dtype=partials, dtype=dtype, keepdims=keepdims,
+                     extra_func_kwargs=dict(dtype=partials))
 
 
 def sum(x, /, *, axis=None, dtype=None, keepdims=False):
@@ -81,8 +92,9 @@ def sum(x, /, *, axis=None, dtype=None, keepdims=False):
         raise TypeError("Only numeric dtypes are allowed in sum")
     if dtype is None:
         dtype = _default_sum_dtype(x.dtype)
-    return reduction(x, _np_sum, axis=axis, dtype=dtype, keepdims=keepdims,
-                     extra_func_kwargs=dict(dtype=dtype))
+    partials = _partials_dtype(dtype)
+    return reduction(x, _np_sum, axis=axis, intermediate_dtype=partials, dtype=dtype, keepdims=keepdims,
+                     extra_func_kwargs=dict(dtype=partials))
 
 
 def cumulative_sum(x, /, *, axis=None, dtype=None, include_initial=False):

@@ -102,8 +102,11 @@ class _NanMeanCombine(ChunkReduction):
     name = "_nanmean_combine"
     structured = True
 
+    # Plain sums: a partial total that is NaN (+inf and -inf met in one chunk)
+    # is a value of the result, as in numpy's nanmean of the whole array; a
+    # NaN-skipping combine dropped that chunk and gave a finite mean.
     def fields(self, in_dtype, kwargs):
-        return [("n", "nansum", in_dtype["n"], "n"), ("total", "nansum", in_dtype["total"], "total")]
+        return [("n", "sum", in_dtype["n"], "n"), ("total", "sum", in_dtype["total"], "total")]
 
 
 class _VarFunc(ChunkReduction):

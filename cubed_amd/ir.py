@@ -74,7 +74,8 @@ def is_bf16(dt) -> bool:
 
 def bf16_to_numpy(a: np.ndarray) -> np.ndarray:
     """bfloat16 bits (the V2 carrier dtype) -> the same values as float32."""
-    return (np.ascontiguousarray(a).view(np.uint16).astype(np.uint32) << 16).view(np.float32)
+    # (ascontiguousarray makes a 0-d array 1-d: the result keeps a's shape)
+    return (np.ascontiguousarray(a).view(np.uint16).astype(np.uint32) << 16).view(np.float32).reshape(np.shape(a))
 
 
 def numpy_to_bf16(a: np.ndarray) -> np.ndarray:

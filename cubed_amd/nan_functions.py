@@ -44,5 +44,11 @@ def nansum(x, /, *, axis=None, dtype=None, keepdims=False):
             dtype = complex128
         else:
             dtype = x.dtype
-    return reduction(x, _np_nansum, axis=axis, dtype=dtype, keepdims=keepdims,
-                     extra_func_kwargs=dict(dtype=dtype))
+    from .array_api.statistical_functions import _np_sum, _partials_dtype
+
+    partials = _partials_dtype(dtype)  # float32 / bfloat16 results: float64 between the rounds
+    # the rounds behind the first combine with a plain sum: a chunk's partial
+    # that is NaN (+inf and -inf in one chunk) belongs to the result, as in
+    # numpy's nansum of the whole array
+    return reduction(x, _np_nansum, combine_func=_np_sum, axis=axis, intermediate_dtype=partials, dtype=dtype, keepdims=keepdims,
+                     extra_func_kwargs=dict(dtype=partials))

@@ -278,7 +278,8 @@ class GpuDagExecutor(DagExecutor):
     def owned_bytes(self) -> int:
         """HBM held by buffers of cached launches and of the executor."""
         total = sum(_nbytes(b) for b in self._scratch)
-        for entry in self._cache.values():
+        # (a copy: an entry goes when its plan is collected, which can happen here)
+        for entry in list(self._cache.values()):
             total += sum(_nbytes(b) for b in entry[2])
         return total
 

@@ -28,6 +28,7 @@ import cubed_amd.array_api as xp
 import vm_model as M
 from cubed_amd import ir
 from cubed_amd import lowering as L
+from gpu_fixtures import arr, interp, jit, spy  # noqa: F401  (the fixtures are used by name)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,46 +73,6 @@ ULP_BASELINE = {
     ("tanh", "float32"): 2, ("tanh", "float64"): 1,        # 1.271, 0.903
 }
 ULP_SLACK = 4
-
-
-# ------------------------------------------------------------------ fixtures
-@pytest.fixture
-def spy(monkeypatch):
-    """[(vtype, mode, has JIT handle)] of every FusedLaunch built."""
-    seen = []
-
-    class Recording(L.FusedLaunch):
-        def __init__(self, prog, *a, **k):
-            super().__init__(prog, *a, **k)
-            seen.append((int(prog.vtype), int(prog.mode), self.handle is not None))
-
-    monkeypatch.setattr(L, "FusedLaunch", Recording)
-    return seen
-
-
-def make_spec(ex):
-    return cubed.Spec(allowed_mem="2GB", reserved_mem="100MB", executor=ex)
-
-
-@pytest.fixture
-def interp(monkeypatch, gpu_executor):
-    """A fresh executor running the ahead-of-time interpreter kernels."""
-    from cubed_amd.runtime.executors.gpu import GpuDagExecutor
-
-    monkeypatch.setenv("CUBED_AMD_JIT", "0")
-    return make_spec(GpuDagExecutor("cuda:0"))
-
-
-@pytest.fixture
-def jit(monkeypatch, gpu_executor):
-    from cubed_amd.runtime.executors.gpu import GpuDagExecutor
-
-    monkeypatch.setenv("CUBED_AMD_JIT", "1")
-    return make_spec(GpuDagExecutor("cuda:0"))
-
-
-def arr(x, chunks, spec):
-    return cubed.from_array(x, chunks=chunks, spec=spec)
 
 
 # ------------------------------------------------------------------ comparison

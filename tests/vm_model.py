@@ -493,3 +493,404 @@ def cast_source(src, dst, n):
         t = np.trunc(v.astype(np.longdouble))
     v = v[np.isfinite(v) & (t >= ii.min) & (t <= ii.max)]
     return np.resize(v, n)
+
+
+# ------------------------------------------------------------------ reductions: kernel forms
+# The geometry table of the reduction conformance tests, in one place:
+# test_reduce_plan.py asserts it on a lower-only dry run, test_gpu_reductions.py
+# on the launches that ran.  Per form: the array, its chunks, the reduced
+# axes, and what the first reduction launch of the plan looks like -- the
+# kernel-form bits of its mode for float32 / float64 / int64 inputs (which
+# may stream) and for every other dtype ("narrow": the narrow and unsigned
+# integers and bool), its tasks, largest kept and reduced extents, whether
+# the reduced extent is split (a workspace on a launch without MODE_PARTIALS)
+# and how many reduction launches the plan has in all.  Mode bits: 1 kernel B
+# (reduced dims last), 4 VEC = 4, 8 streaming, 16 partials (here: lifted).
+FORM_BITS = 1 | 2 | 4 | L.MODE_STREAM | L.MODE_PARTIALS
+
+
+def _form(shape, chunks, axis, modes, ntasks, kept, red, split=False, rounds=1, keepdims=False, mem=None):
+    return dict(shape=shape, chunks=chunks, axis=axis, modes=modes, ntasks=ntasks, kept=kept, red=red,
+                split=split, rounds=rounds, keepdims=keepdims, mem=mem)
+
+
+REDUCE_FORMS = {
+    # kernel A, VEC = 1, a combine round behind it
+    "scalar-axis0": _form((7, 13), (3, 5), 0, (0, 0), 9, 5, 3, rounds=2),
+    "scalar-axis1": _form((7, 13), (3, 5), 1, (0, 0), 9, 3, 5, rounds=2),
+    "scalar-all": _form((7, 13), (3, 5), None, (0, 0), 9, 1, 15, rounds=2),
+    # the streaming kernel unsplit; narrow dtypes: kernel A with VEC = 4
+    "vec4-unsplit": _form((24, 32), (8, 16), 0, (12, 4), 2, 16, 24),
+    # a kept extent (1028) that is no multiple of a wave's 256, two rounds
+    "stream-ragged": _form((70, 1028), (16, 1028), 0, (12, 4), 5, 1028, 16, rounds=2),
+    # the reduced extent split across workgroups, folded by the last to arrive
+    "stream-split": _form((64, 1024), (16, 1024), 0, (12, 4), 1, 1024, 64, split=True),
+    "vec4-split": _form((200, 36), (50, 36), 0, (12, 4), 1, 36, 200, split=True),
+    # kernel B: the reduced dim last
+    "b-vec4": _form((5, 1000), (5, 1000), 1, (5, 5), 1, 5, 1000),
+    "b-scalar": _form((5, 1001), (5, 1001), 1, (1, 1), 1, 5, 1001),
+    "b-split": _form((3, 20000), (3, 10000), 1, (5, 5), 1, 3, 20000, split=True),
+    # a full reduction lifted: the inner dim walked as a kept dim, per-element
+    # partials, then the grouped fold
+    "lifted": _form((64, 4096), (32, 4096), None, (28, 20), 1, 4096, 64),
+    # a full reduction that does not lift (2.2 rows per chunk on average): kernel B, split
+    "full-b-split": _form((70, 4100), (32, 4100), None, (5, 5), 3, 1, 131200, split=True, rounds=2),
+    # 80 chunks along the reduced axis under a small allowed_mem: the merge +
+    # combine rounds fold into one split pass
+    "merge-rounds": _form((400, 64), (5, 64), 0, (12, 4), 1, 64, 400, split=True, mem=120_000),
+    "3d-axes02": _form((9, 10, 11), (4, 5, 6), (0, 2), (0, 0), 12, 5, 24, rounds=2),
+    "3d-axis1-keepdims": _form((9, 10, 11), (4, 5, 6), 1, (0, 0), 6, 24, 10, keepdims=True),
+}
+STREAM_CLASS = ("float32", "float64", "int64")
+
+
+def form_signature(form, leaf):
+    """(vtype, form bits, tasks, kept, red, split) of the first reduction
+    launch of ``form`` over leaves of dtype ``leaf`` (a name of REDUCE_DTYPES)."""
+    f = REDUCE_FORMS[form]
+    vtype = {"float32": L.V_F32, "bfloat16": L.V_F32, "float64": L.V_F64}.get(leaf, L.V_I64)
+    return (vtype, f["modes"][0 if leaf in STREAM_CLASS else 1], f["ntasks"], f["kept"], f["red"], f["split"])
+
+
+def launch_signature(s):
+    """The same of one recorded launch (gpu_fixtures.Seen)."""
+    return (s.vtype, s.mode & FORM_BITS, s.ntasks, s.max_kept, s.max_red, s.split)
+
+
+def assert_form_ran(seen, form, leaves, jit):
+    """``seen`` holds the launches of len(leaves) reductions of ``form``,
+    ``leaves`` naming the dtype each one reads: each reached the form's
+    kernel, with the form's rounds, on the interpreter or the specialised
+    kernels throughout."""
+    red = [s for s in seen if s.nfields > 0]
+    ran = sorted(launch_signature(s) for s in red)
+    wanted = [form_signature(form, leaf) for leaf in leaves]
+    for want in sorted(set(wanted)):
+        assert ran.count(want) == wanted.count(want), (form, want, wanted.count(want), sorted(set(ran)))
+        if want[1] & L.MODE_PARTIALS:
+            assert all(s.ws > 0 for s in red if launch_signature(s) == want)
+    assert len(red) == len(leaves) * REDUCE_FORMS[form]["rounds"], (form, len(red), len(leaves))
+    assert seen and all(s.jit == jit for s in seen), (form, "jit", jit)
+
+
+# ------------------------------------------------------------------ reductions: inputs
+# Every kept element (an output column) of a reduction input tells one
+# story; the stories cycle over the kept elements, and an input with fewer
+# kept elements than stories comes in several variants so that each story is
+# reduced at least once.  A story's special values sit in the first reduced
+# row, the last, the middle or a third of the way in, by the column's turn
+# and the variant, so that they meet different chunks and different splits
+# on the forms with a single kept element too.
+FLOAT_STORIES = ("ordinary", "one_nan", "nan_last_row", "neg_nan", "all_nan", "pos_inf", "both_inf",
+                 "all_neg_zero", "mixed_zero", "all_equal", "negative", "positive", "one_neg_zero")
+INT_STORIES = ("min_and_max", "all_min", "all_max", "all_zero", "single_nonzero", "wrap_sum", "prod_wrap",
+               "prod_zero", "ordinary")
+BOOL_STORIES = ("min_and_max", "all_zero", "all_max", "single_nonzero", "prod_zero", "ordinary")
+REDUCE_DTYPES = ("bool", "int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32",
+                 "float64", "bfloat16")
+NEG_NAN = np.copysign(np.nan, -1.0)
+
+
+def reduce_dtype(name):
+    return ir.bfloat16 if name == "bfloat16" else np.dtype(name)
+
+
+def stories_for(dtype):
+    dt = reduce_dtype(dtype) if isinstance(dtype, str) else np.dtype(dtype)
+    if dt == ir.bfloat16 or dt.kind == "f":
+        return FLOAT_STORIES
+    return BOOL_STORIES if dt.kind == "b" else INT_STORIES
+
+
+def reduce_axes(axis, ndim):
+    if axis is None:
+        return tuple(range(ndim))
+    if isinstance(axis, (int, np.integer)):
+        return (int(axis) % ndim,)
+    return tuple(sorted(int(a) % ndim for a in axis))
+
+
+def reduce_counts(shape, axis):
+    """(reduced count, kept count) of a reduction of ``shape`` over ``axis``."""
+    red = reduce_axes(axis, len(shape))
+    r = int(np.prod([shape[a] for a in red], dtype=np.int64))
+    return r, int(np.prod(shape, dtype=np.int64)) // r
+
+
+def reduce_variants(dtype, shape, axis):
+    """How many inputs it takes for every story to own a kept element."""
+    return -(-len(stories_for(dtype)) // reduce_counts(shape, axis)[1])
+
+
+def prod_exponent_bound(r):
+    """Ordinary factors of a product over ``r`` elements have magnitudes
+    2^u, |u| <= this: the product of any subset then lies within 2^+-100,
+    normal in float64 and in float32 / bfloat16."""
+    return min(0.25, 100.0 / r)
+
+
+def _float_column(story, kind, r, turn, rng):
+    """One kept element's ``r`` reduced values, as float64."""
+    spots = [0, r - 1, r // 2, r // 3]
+    p, q = spots[turn % 4], spots[(turn + 1) % 4]
+    if kind == "prod":
+        b = prod_exponent_bound(r)
+        col = np.exp2(rng.uniform(-b, b, r)) * np.where(rng.random(r) < 0.5, -1.0, 1.0)
+        same = -np.exp2(b)
+    else:
+        col = rng.standard_normal(r) * np.exp(rng.uniform(-3, 3, r))
+        same = 1.5
+    if story == "one_nan":
+        col[p] = np.nan
+    elif story == "nan_last_row":
+        col[r - 1] = np.nan
+    elif story == "neg_nan":
+        col[p] = NEG_NAN
+    elif story == "all_nan":
+        col[:] = np.nan
+        col[q] = NEG_NAN
+    elif story == "pos_inf":
+        col[p] = np.inf
+    elif story == "both_inf":
+        col[p], col[q] = np.inf, -np.inf
+    elif story == "all_neg_zero":
+        col[:] = -0.0
+    elif story == "mixed_zero":
+        col = np.where(rng.random(r) < 0.5, 0.0, -0.0)
+        col[p], col[q] = 0.0, -0.0
+    elif story == "all_equal":
+        col[:] = same
+    elif story == "negative":
+        col = -np.abs(col)
+    elif story == "positive":
+        col = np.abs(col)
+    elif story == "one_neg_zero":
+        col[p] = -0.0
+    else:
+        assert story == "ordinary", story
+    return col
+
+
+def _int_column(story, kind, dt, r, turn, rng):
+    spots = [0, r - 1, r // 2, r // 3]
+    p, q = spots[turn % 4], spots[(turn + 1) % 4]
+    if dt.kind == "b":
+        lo, hi, bits = 0, 1, 1
+    else:
+        lo, hi, bits = int(np.iinfo(dt).min), int(np.iinfo(dt).max), dt.itemsize * 8
+    wide = np.uint64 if dt.kind != "i" else np.int64
+
+    def small():
+        return rng.integers(max(lo, -3) + (dt.kind == "u"), min(hi, 3), r, endpoint=True).astype(wide)
+
+    if story == "ordinary":
+        col = random_fill(dt, r, int(rng.integers(1 << 30))).astype(wide)
+        if kind == "prod" and dt.kind != "b":
+            col |= wide(1)  # odd factors: the wrapped product never collapses to zero
+    elif story == "min_and_max":
+        col = small()
+        col[p], col[q] = lo, hi
+    elif story in ("all_min", "all_max", "all_zero"):
+        col = np.full(r, {"all_min": lo, "all_max": hi, "all_zero": 0}[story], dtype=wide)
+    elif story == "single_nonzero":
+        col = np.zeros(r, dtype=wide)
+        # unsigned: just above the signed type's sign bit (uint64: 2^63 + 1)
+        col[p] = 1 if dt.kind == "b" else -3 if dt.kind == "i" else (1 << (bits - 1)) + 1
+    elif story == "wrap_sum":
+        # near 2^(bits - 2) (signed) / 2^(bits - 1) (unsigned): four of them wrap
+        # a sum of the dtype's own width -- int64 near 2^62, uint64 near 2^63
+        base = 1 << (bits - 2 if dt.kind == "i" else bits - 1)
+        col = (base - 1 + rng.integers(0, 3, r)).astype(wide)
+        if dt.kind == "u":
+            col[q] = base - 1 - (r % 5)  # and one below the sign bit of the signed type
+    else:
+        assert story in ("prod_wrap", "prod_zero"), story
+        # factors of 3 and a few of 2 (2^64 divides a product of 64 of them)
+        col = np.full(r, 3, dtype=wide)
+        twos = min(r // 2, 5 if bits == 8 else 40)
+        col[rng.permutation(r)[:twos]] = 2
+        if story == "prod_zero":
+            col[p] = 0
+    return col.astype(dt)
+
+
+def reduce_inputs(kind, dtype, shape, axis, variant=0, seed=0):
+    """(x, stories): the designed input of a reduction of ``shape`` over
+    ``axis`` and the story of each kept element (an object array of the
+    result's shape without keepdims).  ``kind`` is "prod" for products --
+    ordinary factors within prod_exponent_bound -- and "sum" for every other
+    reduction.  bfloat16 inputs come as float32 values that bfloat16 holds
+    exactly."""
+    dt = reduce_dtype(dtype) if isinstance(dtype, str) else np.dtype(dtype)
+    isfloat = dt == ir.bfloat16 or dt.kind == "f"
+    host = np.dtype("f4") if dt == ir.bfloat16 else dt
+    stories = stories_for(dt)
+    red = reduce_axes(axis, len(shape))
+    kept = tuple(a for a in range(len(shape)) if a not in red)
+    r, k = reduce_counts(shape, axis)
+    rng = np.random.default_rng([seed, variant, kind == "prod", REDUCE_DTYPES.index(
+        "bfloat16" if dt == ir.bfloat16 else dt.name)])
+    cols = np.empty((r, k), dtype=host)
+    names = np.empty(k, dtype=object)
+    for j in range(k):
+        turn, s = divmod(j + variant * k, len(stories))
+        names[j] = stories[s]
+        if isfloat:
+            col = _float_column(stories[s], kind, r, turn + variant + variant // 4, rng)
+            if dt == ir.bfloat16:
+                col = ir.bf16_to_numpy(ir.numpy_to_bf16(col.astype("f4")))
+            cols[:, j] = col.astype(host)
+        else:
+            cols[:, j] = _int_column(stories[s], kind, dt, r, turn + variant + variant // 4, rng)
+    x = cols.reshape([shape[a] for a in red + kept]).transpose(np.argsort(red + kept))
+    return np.ascontiguousarray(x), names.reshape([shape[a] for a in kept])
+
+
+# ------------------------------------------------------------------ reductions: references
+FLOAT_REDUCTIONS = ("sum", "prod", "max", "min", "mean", "any", "all", "nansum", "nanmean")
+INT_REDUCTIONS = ("sum", "prod", "max", "min", "any", "all", "nansum")
+# sum / prod / nansum also run with these explicit result dtypes
+EXPLICIT_DTYPES = {"float32": "float32", "int8": "int8", "int16": "int16", "uint8": "uint64", "uint32": "uint32"}
+
+
+def reduce_cases(dtype):
+    """[(reduction, explicit dtype or None)] a dtype takes.  nanmean, like
+    mean, takes the real floating dtypes only."""
+    dt = reduce_dtype(dtype)
+    if dt.kind == "b":
+        return [("any", None), ("all", None)]
+    fns = FLOAT_REDUCTIONS if dt == ir.bfloat16 or dt.kind == "f" else INT_REDUCTIONS
+    out = [(fn, None) for fn in fns]
+    if dtype in EXPLICIT_DTYPES:
+        out += [(fn, EXPLICIT_DTYPES[dtype]) for fn in ("sum", "prod", "nansum")]
+    return out
+
+
+def reduce_result_dtype(fn, in_dtype, dtype=None):
+    """The array API's result dtype (array_api/statistical_functions.py)."""
+    dt = np.dtype(in_dtype)
+    if fn in ("any", "all"):
+        return np.dtype(bool)
+    if fn in ("sum", "prod", "nansum"):
+        if dtype is not None:
+            return np.dtype(dtype)
+        if dt.kind in "iu":
+            return np.dtype("i8" if dt.kind == "i" else "u8")
+        return np.dtype("f8") if dt == np.dtype("f4") else dt
+    return dt
+
+
+def spacing_in(v, dtype):
+    """np.spacing(|v|) in ``dtype`` (bfloat16: 2^16 float32 spacings at the
+    value cut to bfloat16's bits), as longdouble."""
+    v = np.abs(np.asarray(v))
+    with np.errstate(all="ignore"):
+        if np.dtype(dtype) == ir.bfloat16:
+            cut = (v.astype("f4").view(np.uint32) & np.uint32(0xFFFF0000)).view("f4")
+            return np.spacing(cut).astype(np.longdouble) * 65536
+        return np.spacing(v.astype(dtype)).astype(np.longdouble)
+
+
+def _round_to(ref, dtype):
+    """A longdouble reference rounded to ``dtype``, bfloat16 as float32 values."""
+    with np.errstate(all="ignore"):
+        if np.dtype(dtype) == ir.bfloat16:
+            return ir.bf16_to_numpy(ir.numpy_to_bf16(ref.astype("f4"))).reshape(ref.shape)
+        return ref.astype(dtype)
+
+
+def float_reduce_bounds(fn, x, axis, out_dtype, keepdims=False):
+    """(ref, tol, finite) of a float sum / nansum / prod / mean / nanmean of
+    host values ``x``: the longdouble reference, the allowed error where the
+    reference rounded to the result dtype is finite, and that mask.
+
+    The kernels accumulate float sums in float64 in an order of their own and
+    round once to the result dtype: n additions lose at most n * 2^-53 *
+    sum|v|, the rounding one spacing of the result.  A mean divides that by
+    the count and may lose two spacings (the division, the final rounding).
+    A product of n factors loses at most n * 2^-53 * |prod| and one spacing.
+    Asserted here on the way: sum|v| < max / 2 of the result dtype, so no order
+    of the additions overflows; every subset of a product's finite factors
+    stays normal in float64 and the product normal in the result dtype."""
+    n = reduce_counts(x.shape, axis)[0]
+    kw = dict(axis=axis, keepdims=keepdims)
+    X = x.astype(np.longdouble)
+    host = np.dtype("f4") if np.dtype(out_dtype) == ir.bfloat16 else np.dtype(out_dtype)
+    fi = np.finfo(host)
+    u = np.longdouble(2.0) ** -53
+    with np.errstate(all="ignore"):
+        nan = np.isnan(X)
+        if fn == "prod":
+            ref = np.prod(X, **kw)
+            ok = np.isfinite(X) & (X != 0)
+            log = np.sum(np.abs(np.log2(np.abs(np.where(ok, X, 1)))), **kw)
+            assert np.all(log < 1000), "a subset of the factors could leave float64's normal range"
+            whole = np.isfinite(ref) & (ref != 0)
+            assert np.all((np.abs(ref[whole]) >= fi.tiny) & (np.abs(ref[whole]) <= fi.max / 2)), \
+                "a product is not normal in the result dtype"
+            finite = np.isfinite(_round_to(ref, out_dtype))
+            tol = n * u * np.abs(ref) + spacing_in(_round_to(ref, out_dtype), out_dtype)
+            return ref, tol, finite
+        skip = nan if fn in ("nansum", "nanmean") else np.zeros_like(nan)
+        ref = np.sum(np.where(skip, 0, X), **kw)
+        mag = np.sum(np.where(np.isfinite(X), np.abs(X), 0), **kw)
+        assert np.all(mag < np.longdouble(fi.max) / 2), "the additions could overflow in some order"
+        scale = np.longdouble(1)
+        if fn in ("mean", "nanmean"):
+            count = np.sum(~skip, **kw).astype(np.longdouble)
+            ref = ref / count  # an all-NaN nanmean: 0 / 0
+            scale = np.where(count > 0, count, 1)
+        finite = np.isfinite(_round_to(ref, out_dtype))
+        sp = spacing_in(np.where(finite, _round_to(ref, out_dtype), 0), out_dtype)
+        tol = n * u * mag / scale + (2 if fn in ("mean", "nanmean") else 1) * sp
+    return ref, tol, finite
+
+
+def check_reduction(fn, x, got, axis, in_dtype, dtype=None, keepdims=False, stories=None, what=""):
+    """``got`` (compute()'s numpy result) against the reference of reduction
+    ``fn`` over ``axis`` of host values ``x`` of dtype ``in_dtype``
+    (bfloat16: ``x`` and ``got`` are its values widened to float32).
+
+    Integer and bool results (any / all included) are bit-exact against
+    numpy with the same ``dtype=``: sums and products wrap.  Float max / min:
+    NaN in the same places whatever its sign, else equal values.  Float sum /
+    nansum / prod / mean / nanmean: float_reduce_bounds; NaN and +-inf equal
+    in place and sign.  Two signs of zero are not compared: that of a zero
+    max / min (numpy's own differs between its scalar and SIMD loops) and that
+    of a zero sum -- the kernels' identity is -0.0, so their sum of -0.0s is
+    -0.0, where numpy's own answer has differed between versions (numpy
+    2.2.6 gives +0.0 for np.sum(np.full(n, -0.0)) at every n).  Nothing else
+    is masked; a
+    failure names the stories of the kept elements that differ."""
+    in_dtype = np.dtype(in_dtype)
+    got = np.asarray(got)
+    out_dtype = reduce_result_dtype(fn, in_dtype, dtype)
+    host = np.dtype("f4") if out_dtype == ir.bfloat16 else out_dtype
+    shape = np.empty(x.shape, dtype=bool).sum(axis=axis, keepdims=keepdims).shape
+    assert got.dtype == host, (what, "dtype", got.dtype, host)
+    assert got.shape == shape, (what, "shape", got.shape, shape)
+    kw = dict(axis=axis, keepdims=keepdims)
+    isfloat = in_dtype == ir.bfloat16 or in_dtype.kind == "f"
+    with np.errstate(all="ignore"):
+        if fn in ("any", "all") or not isfloat:
+            npfn = getattr(np, fn)
+            exp = npfn(x, **kw) if fn in ("any", "all", "max", "min") else npfn(x, dtype=out_dtype, **kw)
+            exp = np.asarray(exp)
+            assert exp.dtype == out_dtype, (what, exp.dtype)
+            bad = got != exp
+        elif fn in ("max", "min"):
+            exp = np.asarray(getattr(np, fn)(x, **kw))
+            bad = ~((got == exp) | (np.isnan(got) & np.isnan(exp)))
+        else:
+            ref, tol, finite = float_reduce_bounds(fn, x, axis, out_dtype, keepdims)
+            exp = _round_to(ref, out_dtype)
+            g = got.astype(np.longdouble)
+            bad = np.where(finite, ~(np.abs(g - ref) <= tol),
+                           ~((got == exp) | (np.isnan(got) & np.isnan(exp))))
+            if fn == "prod":  # a zero product's sign is that of its factors'
+                bad |= (exp == 0) & ((got != 0) | (np.signbit(got) != np.signbit(exp)))
+    if np.any(bad):
+        where = np.argwhere(bad)
+        told = sorted(set(np.asarray(stories).reshape(shape)[bad])) if stories is not None else "?"
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} differ, stories {told}; first at "
+                             f"{where[0].tolist()}: got {got[bad][:3]!r}, expected {np.asarray(exp)[bad][:3]!r}")
