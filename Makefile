@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := cubed_amd/csrc
 STREAMS := $(foreach v,f32 f64 i64,$(CSRC)/stream_$(v).hip $(CSRC)/stream_$(v)_split.hip)
-SRCS := $(CSRC)/fused.hip $(STREAMS) $(CSRC)/jit.hip $(CSRC)/copy_random.hip $(CSRC)/scan.hip $(CSRC)/sort.hip $(CSRC)/search.hip $(CSRC)/hist.hip $(CSRC)/unique.hip $(CSRC)/select.hip $(CSRC)/gemm_chain.hip
+SRCS := $(CSRC)/fused.hip $(STREAMS) $(CSRC)/jit.hip $(CSRC)/copy_random.hip $(CSRC)/scan.hip $(CSRC)/sort.hip $(CSRC)/search.hip $(CSRC)/hist.hip $(CSRC)/unique.hip $(CSRC)/select.hip $(CSRC)/gather.hip $(CSRC)/gemm_chain.hip
 CPPSRCS := $(CSRC)/codec.cpp
 OBJS := $(SRCS:.hip=.o) $(CPPSRCS:.cpp=.o)
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -ffp-contract=off \

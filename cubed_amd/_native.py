@@ -161,6 +161,16 @@ SELECT_TASK_DTYPE = np.dtype([
 SELECT_TILE_BYTES = 16384  # CUBED_SELECT_TILE_BYTES: bytes of the run one workgroup owns
 SELECT_COUNT, SELECT_PACK = 0, 1
 
+# cubed_gather_task_t (one index chunk applied to one block of the axis)
+GATHER_TASK_DTYPE = np.dtype([
+    ("src_base", np.int64), ("idx_base", np.int64), ("dst_base", np.int64), ("prev_base", np.int64),
+    ("outer", np.int64), ("n_idx", np.int64), ("n_src", np.int64), ("inner", np.int64),
+    ("lo", np.int64), ("n_total", np.int64),
+])
+GATHER_DIRECT, GATHER_LDS = 0, 1
+GATHER_ELEMS = 4096       # CUBED_GATHER_ELEMS: outputs of one workgroup, direct form
+GATHER_LDS_ELEMS = 16384  # CUBED_GATHER_LDS_ELEMS: most outputs of one workgroup, LDS form
+
 
 class NativeError(RuntimeError):
     pass
@@ -229,6 +239,12 @@ def lib():
     L.cubed_select_work.restype = c_int64
     L.cubed_select_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p]
     L.cubed_select_chunks.restype = c_int
+    L.cubed_gather_tile_bytes.argtypes = []
+    L.cubed_gather_tile_bytes.restype = c_int64
+    L.cubed_gather_path.argtypes = [c_void_p, c_int64, c_int32]
+    L.cubed_gather_path.restype = c_int
+    L.cubed_gather_chunks.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p]
+    L.cubed_gather_chunks.restype = c_int
     L.cubed_gemm_chain_path.argtypes = [c_void_p, c_int64, c_void_p, c_int32, c_int32]
     L.cubed_gemm_chain_path.restype = c_int
     L.cubed_gemm_grid_check.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32]
@@ -335,6 +351,7 @@ EXPORTED_SYMBOLS = (
     "cubed_hist_bins_lds", "cubed_hist_path", "cubed_hist_chunks",
     "cubed_unique_tile", "cubed_unique_work", "cubed_unique_chunks",
     "cubed_select_tile_bytes", "cubed_select_work", "cubed_select_chunks",
+    "cubed_gather_tile_bytes", "cubed_gather_path", "cubed_gather_chunks",
 )
 
 
@@ -423,7 +440,22 @@ def select_work(rows: np.ndarray, esize: int, ignore_sign: bool, kind: int, vsiz
     return work
 
 
-INCLUDE_DIRS = ";".join([os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"),
+def gather_tile_bytes() -> int:
+    """The most bytes of a source row one workgroup of the gather stages whole
+    in LDS (host only)."""
+    return int(lib().cubed_gather_tile_bytes())
+
+
+def gather_path(rows: np.ndarray, esize: int) -> int:
+    """The kernel form a host table of GATHER_TASK_DTYPE rows takes (host only)."""
+    rows = np.ascontiguousarray(rows, dtype=GATHER_TASK_DTYPE)
+    path = lib().cubed_gather_path(rows.ctypes.data, len(rows), esize)
+    if path < 0:
+        check(path, "cubed_gather_path")
+    return path
+
+
+INCLUDE_DIRS =";".join([os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"),
                          os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")])
 
 

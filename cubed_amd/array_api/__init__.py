@@ -41,7 +41,7 @@ from .dtypes import (
 from .elementwise_functions import *  # noqa: F401,F403
 from .elementwise_functions import abs, round  # noqa: F401
 from .linear_algebra_functions import matmul, matrix_transpose, outer, tensordot, vecdot
-from .indexing_functions import take
+from .indexing_functions import take, take_along_axis
 from .manipulation_functions import (
     broadcast_arrays,
     broadcast_to,

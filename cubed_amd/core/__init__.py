@@ -20,6 +20,7 @@ from .ops import (
     sort_network,
     squeeze,
     store,
+    take_along_axis,
     to_zarr,
     tree_reduce,
     unify_chunks,
@@ -32,6 +33,6 @@ from .plan import Plan
 __all__ = [
     "CoreArray", "Plan", "blockwise", "compute", "elemwise", "from_array", "from_device", "from_zarr",
     "gensym", "histogram", "map_blocks", "map_direct", "measure_reserved_mem", "merge_chunks",
-    "partial_reduce", "rechunk", "reduction", "scan", "searchsorted", "select_count", "select_pack", "sort", "sort_network", "squeeze", "store", "to_zarr", "tree_reduce",
+    "partial_reduce", "rechunk", "reduction", "scan", "searchsorted", "select_count", "select_pack", "sort", "sort_network", "squeeze", "store", "take_along_axis", "to_zarr", "tree_reduce",
     "unify_chunks", "unique_count", "unique_gather", "unique_pack", "visualize",
 ]

@@ -1006,6 +1006,53 @@ def searchsorted(x1: "Array", x2: "Array", right: bool = False) -> "Array":
     return counts
 
 
+# ------------------------------------------------------------------ gathers (take_along_axis)
+
+
+class _gather_block_function:
+    """Output block ``c`` of the gather from block ``b`` of the axis reads
+    chunk ``c`` of the indices, the chunk of ``x`` at ``c`` with the axis
+    coordinate replaced by ``b`` and, after the first block, chunk ``c`` of the
+    result so far."""
+
+    def __init__(self, idx_name, x_name, axis, b, prev_name=None):
+        self.idx_name, self.x_name, self.axis, self.b, self.prev_name = idx_name, x_name, axis, b, prev_name
+
+    def __call__(self, out_key):
+        coords = tuple(out_key[1:])
+        keys = [(self.idx_name,) + coords,
+                (self.x_name,) + coords[:self.axis] + (self.b,) + coords[self.axis + 1:]]
+        if self.prev_name is not None:
+            keys.append((self.prev_name,) + coords)
+        return keys
+
+
+def take_along_axis(x: "Array", idx: "Array", axis: int) -> "Array":
+    """``np.take_along_axis(x, idx, axis)`` for an int64 ``idx`` of ``x``'s
+    number of dimensions, extents and chunks off ``axis`` (``0 <= axis <
+    ndim``), neither empty: the shape and chunks of ``idx``, the dtype of
+    ``x`` (real, 1, 2, 4 or 8 bytes).  An index ``i`` in ``[-n, 0)`` means
+    ``i + n``; one outside ``[-n, n)`` gives a zero element.
+
+    An output chunk may need any block of ``x`` along the axis and no task may
+    hold them all, so with ``nb`` blocks the plan is ``nb`` chained ops: op
+    ``b`` writes the elements whose index falls in block ``b`` and keeps the
+    result of op ``b - 1`` (zero in op 0) elsewhere.  A task reads one chunk
+    of ``idx``, one chunk of ``x`` and (after the first op) one chunk of the
+    result so far, never more, and every op passes the ordinary
+    projected-memory check.  The price is ``nb`` passes over ``idx``: one read
+    of the indices and one read and one write of the result per block."""
+    dtype = np.dtype(x.dtype)
+    out = None
+    for b in range(x.numblocks[axis]):
+        args = (idx, x) if out is None else (idx, x, out)
+        out = general_blockwise(
+            ir.GatherProgram(axis=int(axis), dtype=dtype, nargs=len(args)),
+            _gather_block_function(idx.name, x.name, axis, b, None if out is None else out.name),
+            *args, shape=idx.shape, dtype=dtype, chunks=idx.chunks, extra_projected_mem=0, fusable=False)
+    return out
+
+
 # ------------------------------------------------------------------ run heads (unique_*)
 
 

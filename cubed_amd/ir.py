@@ -536,6 +536,22 @@ class SelectProgram(Program):
     name: str = "select"
 
 
+@dataclass(frozen=True, eq=False)
+class GatherProgram(Program):
+    """Per task (take_along_axis): one chunk of int64 indices, argument 0,
+    applied along ``axis`` to one chunk of argument 1, an array of ``dtype``
+    (any real dtype of 1, 2, 4 or 8 bytes) that is one block of the axis: an
+    output element whose index, wrapped once if negative, falls in that block
+    gets the element there; every other one gets the element of argument 2,
+    the chunk of the result over the earlier blocks (``nargs=3``), or zero
+    (``nargs=2``).  Not an expression program: never fused, and the rewrites
+    leave it alone."""
+    axis: int = 0
+    dtype: np.dtype = np.dtype("float64")
+    nargs: int = 2
+    name: str = "take_along_axis"
+
+
 def sort_pairs_dtype(dtype) -> np.dtype:
     """Element type of the arrays a pairs-mode sort works on."""
     return np.dtype([("v", np.dtype(dtype)), ("i", np.int64)])

@@ -847,6 +847,91 @@ class SelectLaunch:
                                                 self.work, stream), "cubed_select_chunks")
 
 
+# ------------------------------------------------------------------ gathers (take_along_axis)
+
+
+def gather_esize(dtype) -> int:
+    """Element size of a dtype the gather moves as bits."""
+    dtype = np.dtype(dtype)
+    if dtype.names or dtype.kind == "c" or dtype.itemsize not in (1, 2, 4, 8):
+        raise LoweringError(f"take_along_axis of {dtype} elements is not lowered")
+    return dtype.itemsize
+
+
+def gather_task(src: ArrView, idx: ArrView, dst: ArrView, axis: int, lo: int, n_total: int,
+                prev: Optional[ArrView] = None):
+    """One nat.GATHER_TASK_DTYPE row: the int64 chunk view ``idx`` applied along
+    ``axis`` to the chunk view ``src``, which holds the places ``[lo, lo +
+    src.extent[axis])`` of an axis of ``n_total``, into ``dst``, on top of the
+    earlier result ``prev`` if given.  ``dst`` and ``prev`` have ``idx``'s
+    extent and ``src``'s dtype; ``src`` has ``idx``'s extent off the axis.
+    All views are compact and C-ordered, so each is (outer, n, inner)."""
+    for v in (src, idx, dst, prev):
+        if v is not None and list(v.stride) != list(c_strides(list(v.extent))):
+            raise LoweringError("take_along_axis chunks must be compact and C-ordered")
+    nd = len(idx.extent)
+    if not 0 <= axis < nd or len(src.extent) != nd:
+        raise LoweringError(f"take_along_axis along axis {axis} of chunks of extent {list(src.extent)} and "
+                            f"{list(idx.extent)}")
+    if np.dtype(idx.dtype) != np.int64:
+        raise LoweringError(f"take_along_axis indices of {idx.dtype}, not int64")
+    off = [d for d in range(nd) if d != axis]
+    if [src.extent[d] for d in off] != [idx.extent[d] for d in off]:
+        raise LoweringError(f"take_along_axis: an index chunk of extent {list(idx.extent)} over a chunk of extent "
+                            f"{list(src.extent)} along axis {axis}")
+    for v in (dst, prev):
+        if v is not None and (np.dtype(v.dtype) != np.dtype(src.dtype) or list(v.extent) != list(idx.extent)):
+            raise LoweringError(f"take_along_axis result chunk ({v.dtype}, extent {list(v.extent)}) does not match "
+                                f"its index chunk of extent {list(idx.extent)} and {src.dtype} elements")
+    if lo < 0 or lo + src.extent[axis] > n_total:
+        raise LoweringError(f"take_along_axis: block [{lo}, {lo + src.extent[axis]}) of an axis of {n_total}")
+    row = np.zeros((), dtype=nat.GATHER_TASK_DTYPE)
+    row["src_base"], row["idx_base"], row["dst_base"] = src.base, idx.base, dst.base
+    row["prev_base"] = prev.base if prev is not None else 0
+    row["outer"], row["inner"] = math.prod(idx.extent[:axis]), math.prod(idx.extent[axis + 1:])
+    row["n_idx"], row["n_src"] = idx.extent[axis], src.extent[axis]
+    row["lo"], row["n_total"] = lo, n_total
+    return row
+
+
+class GatherLaunch:
+    """One cubed_gather_chunks launch: a device table of gather tasks (one per
+    output chunk).  The kernel form is chosen once for the whole table, on the
+    host (cubed_gather_path); ``path=nat.GATHER_DIRECT`` forces the form that
+    is correct for every table.  ``sink``: the list of buffers the cache entry
+    being built owns; the table joins it."""
+
+    def __init__(self, rows: np.ndarray, esize: int, device, sink=None, path: Optional[int] = None):
+        import torch
+
+        self.ntasks = len(rows)
+        self.rows = rows
+        self.esize = esize
+        self.path, self.work = nat.GATHER_DIRECT, 0
+        if self.ntasks == 0:
+            return
+        chosen = nat.gather_path(rows, esize)  # validates the table
+        if path is None:
+            path = chosen
+        elif path not in (nat.GATHER_DIRECT, chosen):
+            raise LoweringError("take_along_axis: the LDS form does not apply to this table")
+        self.path = path
+        outer, n_idx, inner = (rows[f].astype(object) for f in ("outer", "n_idx", "inner"))
+        if path == nat.GATHER_LDS:
+            self.work = int(max(outer * (-(-n_idx // nat.GATHER_LDS_ELEMS))))
+        else:
+            self.work = int(max(-(-(outer * n_idx * inner) // nat.GATHER_ELEMS)))
+        self.table = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).copy()).to(device)
+        if sink is not None:
+            sink.append(self.table)
+
+    def run(self, stream):
+        if self.ntasks == 0 or self.work == 0:
+            return
+        nat.check(nat.lib().cubed_gather_chunks(self.table.data_ptr(), self.ntasks, self.esize, self.path,
+                                                self.work, stream), "cubed_gather_chunks")
+
+
 # ------------------------------------------------------------------ programs
 
 

@@ -157,12 +157,12 @@ def general_blockwise(
 
 
 def is_fuse_candidate(op: PrimitiveOperation) -> bool:
-    # a scan, a sort, a search, a histogram, a run-head or a select op is its own launch under every optimizer
-    # (the linear-chain fusion of simple_optimize_dag does not look at ``fusable``)
+    # a scan, a sort, a search, a histogram, a run-head, a select or a gather op is its own launch under every
+    # optimizer (the linear-chain fusion of simple_optimize_dag does not look at ``fusable``)
     return op.pipeline.function is apply_blockwise and \
         not isinstance(op.pipeline.config.function,
                        (ir.ScanProgram, ir.SortProgram, ir.SearchProgram, ir.HistogramProgram,
-                        ir.UniqueProgram, ir.SelectProgram))
+                        ir.UniqueProgram, ir.SelectProgram, ir.GatherProgram))
 
 
 def can_fuse_primitive_ops(op1: PrimitiveOperation, op2: PrimitiveOperation) -> bool:

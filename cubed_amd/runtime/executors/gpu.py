@@ -400,7 +400,7 @@ class GpuDagExecutor(DagExecutor):
             if isinstance(program, (ir.ExprProgram, ir.MatmulProgram, ir.TensordotProgram,
                                     ir.PerBlockProgram, ir.ScanProgram, ir.SortProgram,
                                     ir.SearchProgram, ir.HistogramProgram, ir.UniqueProgram,
-                                    ir.SelectProgram)):
+                                    ir.SelectProgram, ir.GatherProgram)):
                 return self._lower_part(program, cfg, target, keys)
             if isinstance(program, ir.GemmThenProgram):
                 from types import SimpleNamespace
@@ -459,6 +459,9 @@ class GpuDagExecutor(DagExecutor):
         if isinstance(program, ir.SelectProgram):
             raise LoweringError("nonzero and boolean-mask indexing run on one GPU only: their select launches "
                                 f"are not lowered for a world of {self.world} ranks")
+        if isinstance(program, ir.GatherProgram):
+            raise LoweringError("take_along_axis runs on one GPU only: its gather launches are not "
+                                f"lowered for a world of {self.world} ranks")
         if isinstance(program, ir.ExprProgram) and program.reduce is not None and \
                 any(isinstance(l, ir.Region) for l in ir.leaves_of_program(program)) and \
                 not any(isinstance(l, ir.Concat) for l in ir.leaves_of_program(program)):
@@ -622,6 +625,8 @@ class GpuDagExecutor(DagExecutor):
             return [self._lower_unique(program, cfg, target, keys)]
         if isinstance(program, ir.SelectProgram):
             return [self._lower_select(program, cfg, target, keys)]
+        if isinstance(program, ir.GatherProgram):
+            return [self._lower_gather(program, cfg, target, keys)]
         return [self._lower_gemm(program, cfg, target, keys)]
 
     def _task_reads(self, program, cfg, key, regions=True):
@@ -964,6 +969,37 @@ class GpuDagExecutor(DagExecutor):
             rows[i] = select_task(ins[0][1], ins[1][1] if values else None, chunk_view(target, key),
                                   ins[0][0].chunk_start((b,))[0], program.kind, program.payload)
         return SelectLaunch(rows, esize, ignore_sign, program.kind, vsize, self.device, self._sink, self.scratch)
+
+    def _lower_gather(self, program, cfg, target, keys):
+        """One gather task per output chunk (ir.GatherProgram): the chunk of
+        the indices with the output chunk's extent, one chunk of the source --
+        a block of the axis -- and, with three arguments, the chunk of the
+        result over the earlier blocks."""
+        from ...lowering import GatherLaunch, gather_esize, gather_task
+
+        esize = gather_esize(program.dtype)
+        if np.dtype(target.dtype) != np.dtype(program.dtype):
+            raise LoweringError(f"take_along_axis of {program.dtype} elements into a {target.dtype} array")
+        rows = np.zeros(len(keys), dtype=nat.GATHER_TASK_DTYPE)
+        for i, key in enumerate(keys):
+            args = cfg.block_function(("out",) + tuple(key))
+            if len(args) != program.nargs or program.nargs not in (2, 3):
+                raise LoweringError(f"take_along_axis program with {len(args)} inputs")
+            ins = []
+            for a, dt in zip(args, (np.int64, program.dtype, program.dtype)):
+                if not isinstance(a, tuple):
+                    raise LoweringError("a take_along_axis task reads whole single chunks only")
+                src = self.device_source(cfg.reads_map[a[0]].array)
+                if not isinstance(src, DeviceArray) or np.dtype(src.dtype) != np.dtype(dt):
+                    raise LoweringError(f"take_along_axis input {a[0]} is not a device array of {np.dtype(dt)}")
+                ins.append((src, tuple(a[1:])))
+            (x, xc) = ins[1]
+            if not 0 <= program.axis < x.ndim:
+                raise LoweringError(f"take_along_axis along axis {program.axis} of a {x.ndim}-d array")
+            rows[i] = gather_task(chunk_view(x, xc), chunk_view(*ins[0]), chunk_view(target, key), program.axis,
+                                  x.chunk_start(xc)[program.axis], x.shape[program.axis],
+                                  chunk_view(*ins[2]) if program.nargs == 3 else None)
+        return GatherLaunch(rows, esize, self.device, self._sink)
 
     def zero_page(self) -> int:
         """Device address of 4 KiB of zeros (k past a GEMM chain's end)."""
@@ -1476,8 +1512,9 @@ class GpuDagExecutor(DagExecutor):
                     total += t.device_bytes()
                 else:  # this rank's block-cyclic share, at most
                     total += -(-t.nchunks // self.world) * sum(t.slot_bytes(f) for f in t.fields)
-        # uploaded host / in-memory sources are replicated on every rank
-        total += sum(d.device_bytes() for d in self._uploads.values() if d.allocated)
+        # uploaded host / in-memory sources are replicated on every rank.  A snapshot: a collection
+        # that runs inside the loop may finalize a source array, and _drop_upload then pops its entry
+        total += sum(d.device_bytes() for d in list(self._uploads.values()) if d.allocated)
         self._resident_bytes = total
         # scratch gathers and split temporaries of cached launches
         total += self.owned_bytes()

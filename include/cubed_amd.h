@@ -54,6 +54,10 @@
  *   cubed_select_chunks  -> no reference interface: nonzero and boolean-mask
  *                           indexing are not in the reference either; the
  *                           semantics are numpy's flatnonzero and a[mask].
+ *   cubed_gather_chunks  -> no reference interface: the reference notes that
+ *                           the Array API lacked take_along_axis
+ *                           (cubed/core/ops.py:1124,1145); the semantics are
+ *                           numpy's take_along_axis of one block of the axis.
  */
 #ifndef CUBED_AMD_H
 #define CUBED_AMD_H
@@ -675,6 +679,50 @@ int64_t cubed_select_work(const cubed_select_task_t* tasks, int64_t ntasks, int3
  * (ntasks x work).  Neither synchronises nor allocates. */
 int cubed_select_chunks(const cubed_select_task_t* d_tasks, int64_t ntasks, int32_t esize,
                         int32_t ignore_sign, int32_t kind, int32_t vsize, int64_t work, void* stream);
+
+/* Gathering along one axis (take_along_axis; new symbols only, the ABI version
+ * is unchanged).  A task has an int64 index chunk seen as (outer, n_idx, inner),
+ * a source chunk (outer, n_src, inner) of elements of esize bytes (1, 2, 4 or
+ * 8) that holds the places [lo, lo + n_src) of an axis of n_total places, a
+ * destination chunk and, if prev_base is not 0, an earlier result, both of the
+ * index chunk's extent and of esize bytes.  All four are compact and C-ordered.
+ * For every (o, j, k), with i = idx[o][j][k], plus n_total if i < 0:
+ *   dst[o][j][k] = src[o][i - lo][k]                 if lo <= i < lo + n_src
+ *                = prev_base ? prev[o][j][k] : 0     otherwise.
+ * That guard is on every read of src, so no index, however far out of range,
+ * reaches memory outside the source chunk.  Elements move as bits.  The
+ * destination is never one of the inputs.  No workgroup waits for, signals or
+ * reads the output of another one and there are no atomics: results are
+ * bit-identical run to run. */
+#define CUBED_GATHER_TILE_BYTES 32768 /* most bytes of a source row the LDS form stages */
+#define CUBED_GATHER_ELEMS 4096       /* outputs of one workgroup, direct form */
+#define CUBED_GATHER_LDS_ELEMS 16384  /* most outputs of one workgroup, LDS form (one row) */
+#define CUBED_GATHER_DIRECT 0         /* paths: every read of src goes to global memory */
+#define CUBED_GATHER_LDS 1            /* inner == 1: the source row is staged in LDS */
+
+typedef struct {
+  int64_t src_base, idx_base, dst_base;  /* device byte addresses */
+  int64_t prev_base;                     /* 0 = none */
+  int64_t outer, n_idx, n_src, inner;    /* elements */
+  int64_t lo, n_total;                   /* the source chunk's start on the axis; the axis */
+} cubed_gather_task_t;
+
+/* Host only: CUBED_GATHER_TILE_BYTES of the loaded library. */
+int64_t cubed_gather_tile_bytes(void);
+/* Host only (no device call): validates a HOST copy of a gather task table and
+ * returns the path of its launch: CUBED_GATHER_LDS when every task that writes
+ * anything has inner == 1, n_src * esize <= CUBED_GATHER_TILE_BYTES and
+ * n_idx >= n_src, else CUBED_GATHER_DIRECT; a negative CUBED_E_* code for a
+ * malformed table. */
+int cubed_gather_path(const cubed_gather_task_t* tasks, int64_t ntasks, int32_t esize);
+/* One launch over a DEVICE task table.  work = the most workgroups any task
+ * needs: ceil(outer * n_idx * inner / CUBED_GATHER_ELEMS) in the direct form,
+ * outer * ceil(n_idx / CUBED_GATHER_LDS_ELEMS) in the LDS form.
+ * CUBED_GATHER_DIRECT is correct for every table, CUBED_GATHER_LDS only for
+ * the tables cubed_gather_path gives it to; both write the same bytes there.
+ * Neither synchronises nor allocates. */
+int cubed_gather_chunks(const cubed_gather_task_t* d_tasks, int64_t ntasks, int32_t esize, int32_t path,
+                        int64_t work, void* stream);
 
 /* Chained chunk GEMMs (blockwise matmul / tensordot with the k-sum fused):
  * task t computes C_t (=|+=) sum over its segments s of A_s @ B_s, row-major
